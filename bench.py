@@ -1,22 +1,28 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet|wsi|simclr]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet|wsi|simclr] [--full] [--dump-outputs DIR]
 
-One command covers BASELINE.json's whole metric.  Default workload (configs[1]): batched ResNet18 bf16
-inference over synthetic 224x224 patches already resident in HBM as uint8 HWC; one STEP = one pass of the hot
-path over one batch of 8192 patches (ToTensor/Normalize folded into the stem kernel + the MFMA ResNet18
-forward -> features [B,512], logits [B,2], argmax labels); 8 steps = the 64k patches of the config.  The same
-JSON line also carries
+Default workload (configs[1]): batched ResNet18 bf16 inference over synthetic 224x224 patches already resident
+in HBM as uint8 HWC; one STEP = one pass of the hot path over one batch of 8192 patches (ToTensor/Normalize
+folded into the stem kernel + the MFMA ResNet18 forward -> features [B,512], logits [B,2], argmax labels);
+8 steps = the 64k patches of the config.  A plain run sets up, warms up, times the K steps and prints one JSON
+line with the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and nothing else.
+`--dump-outputs DIR` then writes what the timed path returned in its last step as DIR/<name>.npy (float32 /
+float64, at most 64 MB in all: a fixed, seeded row sample of larger outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+`--full` covers BASELINE.json's whole metric: the same JSON line then also carries
   "wsi"          -- configs[2] and north_star's 100k slide: whole-slide hierarchical scan (levels 0-3, reference
                     grid), s/slide, kept patches/s, the level-0 resampler's HBM roofline, CPU extractor baseline
   "parity"       -- max norm-relative error of features / logits and label mismatches of every precision against
                     the fp32 oracle on the first 256 patches of the workload (configs[0]), outside the timed region
   "roofline"     -- dominant kernel: algorithmic FLOPs per launch / average launch duration (HIP events, launch stream)
   "cpu_baseline" -- configs[0]: the oracle on the host cores, batch 256 (and 512), warm-up + timed iterations, median
+and the per-op table, the other precisions, the parity modes, the PCIe-inclusive step and the `simclr` object.
 `--workload wsi` makes the whole-slide scan the timed step (with --gpus N: configs[3], one slide per rank and
-one ragged all-gather of features + logits + meta); `--workload simclr` times the native SimCLR training step
-(configs[4]).
+one ragged all-gather of features + logits + meta; `--full` adds its resampler roofline and CPU baseline);
+`--workload simclr` times the native SimCLR training step (configs[4]; `--full` adds its input pipeline).
 
 --gpus N > 1: when not already under torch.distributed.run (no WORLD_SIZE in the environment) this process
 only LAUNCHES: it starts N fresh child processes, one rank per GPU (RCCL), before anything touches the GPU,
@@ -111,6 +117,29 @@ def host_threads() -> int:
     except (OSError, ValueError):
         pass
     return max(1, n)
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """`--dump-outputs`: one DIR/<name>.npy per output of the timed path's last step, float64 kept, everything else as
+    float32 (labels and indices are exact in it).  When the set exceeds `limit` bytes every array keeps the same fixed,
+    seeded choice of rows (arrays with the same row count: the same rows), ascending, so runs stay comparable."""
+    import numpy as np
+
+    host = {k: (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy() for k, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > limit:
+        for k, a in host.items():
+            if a.ndim == 0:
+                continue
+            keep = max(1, int(a.shape[0] * limit / total))
+            rows = np.sort(np.random.default_rng(20250101).choice(a.shape[0], keep, replace=False))
+            host[k] = a[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def per_op_times(net: capi.PackedResNet18, dev, reps: int = 20):
@@ -252,8 +281,9 @@ def planes_roofline(slide, side):
             "bytes_per_launch": w0 * h0 * 3}
 
 
-def scan_slide_timed(net, slide, args, world, steps, warmup, dev):
-    """Time `steps` whole-slide scans (levels 0-3).  Returns (seconds per slide, windows, kept)."""
+def scan_slide_timed(net, slide, args, world, steps, warmup, dev, keep_last=False):
+    """Time `steps` whole-slide scans (levels 0-3).  Returns (seconds per slide, windows, kept).  `keep_last`: this
+    rank's (features, logits, labels, meta) of the last scan are left in `scan_slide_timed.last_out`."""
     from ss25_hierarchical_multiscale_image_classification_amd import extract
 
     stride_of = (lambda lvl: None) if args.grid == "reference" else (lambda lvl: extract.PATCH_SIZES[lvl])
@@ -266,6 +296,8 @@ def scan_slide_timed(net, slide, args, world, steps, warmup, dev):
         f, l, p, meta = extract.score_slide(slide, net, levels=(0, 1, 2, 3), batch_windows=args.batch_windows,
                                             stride=stride_of)
         n_local = f.shape[0]
+        if keep_last:
+            scan_slide_timed.last_out = (f, l, p, meta)
         if world > 1:  # configs[3]: the one exchange of the path -- ragged all-gather, rank-major order
             f, l, meta = hdist.gather_results(f, l, meta)
         return n_local
@@ -378,6 +410,10 @@ def run_resnet(args, rank, world, dev):
         "tflops_whole_path": value * FLOP_PER_PATCH / 1e12 / world,
         "frac_of_peak_whole_path": value * FLOP_PER_PATCH / 1e12 / world / PEAK_BF16_DENSE_TFLOPS,
     }
+    if args.dump_outputs and rank == 0:  # the last step's results (N > 1: rank 0's features, the gathered logits / labels)
+        dump_outputs(args.dump_outputs, {"features": out[0], "logits": out[1], "labels": out[2]})
+    if not args.full:
+        return rec
     if rank == 0:
         ops = per_op_times(net, dev)
         convs = [o for o in ops if o["tflops"]]
@@ -622,10 +658,15 @@ def run_wsi(args, rank, world, dev):
     side = args.slide_side
     net = capi.PackedResNet18(synth.seeded_resnet18_state_dict(0, num_classes=2), precision=args.precision)
     slide = extract.DeviceSlide.synthetic(side, side, seed=10 + rank, with_polygons=True)
-    s_per, n_all, n_kept = scan_slide_timed(net, slide, args, world, args.steps, args.warmup, dev)
+    s_per, n_all, n_kept = scan_slide_timed(net, slide, args, world, args.steps, args.warmup, dev,
+                                            keep_last=bool(args.dump_outputs) and rank == 0)
     unique_bytes = sum(w * h * 3 for (w, h) in slide.level_dimensions)
     extra = dict(getattr(scan_slide_timed, "rank_stats", None) or {})
-    if rank == 0:
+    if args.dump_outputs and rank == 0:
+        f, l, p, meta = scan_slide_timed.last_out
+        dump_outputs(args.dump_outputs, {"features": f, "logits": l, "labels": p, "meta": meta})
+        del scan_slide_timed.last_out, f, l, p, meta
+    if rank == 0 and args.full:
         extra["roofline"] = planes_roofline(slide, side)
         if world == 1 and not args.no_cpu_baseline:
             extra["cpu_baseline"] = cpu_baseline_wsi()
@@ -648,7 +689,9 @@ def run_simclr(args, rank, world, dev):
     from ss25_hierarchical_multiscale_image_classification_amd import train_native
 
     rec = train_native.bench_simclr_step(args, rank, world, dev)
-    if world == 1:  # what feeds the step: both views made on the device from patches resident in HBM, next to the host's Pillow path
+    if args.dump_outputs and rank == 0:  # what the step returns: the loss of the last step
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([rec["final_loss"]], dtype=torch.float64)})
+    if world == 1 and args.full:  # what feeds the step: both views made on the device from patches resident in HBM, next to the host's Pillow path
         from ss25_hierarchical_multiscale_image_classification_amd import augment
         rec["input_pipeline"] = augment.bench_input_pipeline(n_pairs=min(args.simclr_views, 1024), P=224, steps=5, device=dev)
     return rec
@@ -680,6 +723,11 @@ def build_parser():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=["resnet", "wsi", "simclr"], default="resnet")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-op table and roofline, other precisions, parity modes and oracle parity, "
+                         "CPU baselines, the wsi / tiff / simclr objects (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--precision", choices=["bf16", "fp16"], default="bf16")
     ap.add_argument("--batch", type=int, default=8192, help="patches per step per GPU")
     ap.add_argument("--slide_side", type=int, default=50000)

@@ -1,4 +1,4 @@
-"""Generate tests/golden/mil_golden.npz + mil_dataset_ref.json.  Run in the BUILD container:
+"""Generate tests/golden/mil_golden.npz + mil_golden_bags.npz + mil_dataset_ref.json:
 
     python tests/golden/make_golden_mil.py
 
@@ -47,7 +47,9 @@ def main():
                 out[f"{pooling}.logits{i}"] = logits.numpy()
                 if attn is not None:
                     out[f"{pooling}.attn{i}"] = attn.numpy()
-    np.savez_compressed(os.path.join(HERE, "mil_golden.npz"), **out)
+    # the input bags in a file of their own: each file stays under the 1 MiB a committed file may take
+    np.savez_compressed(os.path.join(HERE, "mil_golden_bags.npz"), **{k: v for k, v in out.items() if k.startswith("bag")})
+    np.savez_compressed(os.path.join(HERE, "mil_golden.npz"), **{k: v for k, v in out.items() if not k.startswith("bag")})
 
     # dataset grouping: the reference's WSIMILDDataset on a small (features, labels, paths) triple
     names = []
@@ -74,7 +76,7 @@ def main():
             bags_out.append({"rows": idx, "wsi_label": int(y)})
     json.dump({"paths": names, "labels": labels.tolist(), "bags": bags_out},
               open(os.path.join(HERE, "mil_dataset_ref.json"), "w"), indent=0)
-    print("wrote mil_golden.npz, mil_dataset_ref.json:", len(out), "arrays,", len(bags_out), "bags")
+    print("wrote mil_golden.npz, mil_golden_bags.npz, mil_dataset_ref.json:", len(out), "arrays,", len(bags_out), "bags")
 
 
 if __name__ == "__main__":

@@ -216,13 +216,13 @@ def test_single_rank_rccl_drives_every_exchange(tmp_path):
 
 
 def test_bench_two_ranks_default_line(tmp_path):
-    """`bench.py --gpus 2` as the driver starts it (here: both ranks on cuda:0 over gloo): the parent launches two fresh
-    ranks, each runs the default workload on its own patches / slide / views, rank 0 prints ONE JSON line whose value is the
-    aggregate over both ranks and whose `wsi` and `simclr` objects come from the sharded runs."""
+    """`bench.py --gpus 2 --full` (here: both ranks on cuda:0 over gloo): the parent launches two fresh ranks, each runs
+    the default workload on its own patches / slide / views, rank 0 prints ONE JSON line whose value is the aggregate over
+    both ranks and whose `wsi` and `simclr` objects come from the sharded runs."""
     import json
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one_device", "--steps", "2",
-           "--warmup", "1", "--batch", "1024", "--no_cpu_baseline", "--wsi_sides", "3000", "--rank_timeout", "800"]
+           "--warmup", "1", "--batch", "1024", "--full", "--no_cpu_baseline", "--wsi_sides", "3000", "--rank_timeout", "800"]
     r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -131,3 +131,35 @@ def test_bench_launcher_builds_one_process_per_rank():
     assert bench.host_threads() >= 1
     assert bench.kernel_of("l1b0") == "block16_c64_kernel" and bench.kernel_of("l3b1c1") == "conv3x3_halo16_kernel"
     assert [n for n, _ in bench.OPS][2:6] == ["l1b0", "(fused)", "l1b1", "(fused)"]  # a layer1 BasicBlock is one launch
+
+
+def test_bench_full_flag_and_output_dump(tmp_path):
+    """A plain bench run is the headline only (`--full` adds the rest); `--dump-outputs DIR` writes float32 / float64 .npy
+    files, and past its byte limit every array keeps the same seeded rows."""
+    import bench
+
+    args = bench.build_parser().parse_args([])
+    assert args.full is False and args.dump_outputs is None
+    args = bench.build_parser().parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert args.full is True and args.dump_outputs == str(tmp_path)
+
+    g = torch.Generator().manual_seed(3)
+    feats = torch.randn(100, 8, generator=g).to(torch.bfloat16)
+    logits = torch.randn(100, 2, generator=g)
+    labels = logits.argmax(1)
+    loss = torch.tensor([1.25], dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), {"features": feats, "logits": logits, "labels": labels, "loss": loss})
+    f = np.load(tmp_path / "all" / "features.npy")
+    assert f.dtype == np.float32 and np.array_equal(f, feats.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "labels.npy"), labels.numpy().astype(np.float32))
+    assert np.load(tmp_path / "all" / "loss.npy").dtype == np.float64
+
+    limit = 2000  # 100 x (8 + 2 + 1) floats = 4400 bytes: sampled to fewer than half the rows
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"features": feats, "logits": logits, "labels": labels}, limit=limit)
+    got = {k: np.load(tmp_path / "s1" / f"{k}.npy") for k in ("features", "logits", "labels")}
+    assert sum(a.nbytes for a in got.values()) <= limit
+    assert all(np.array_equal(got[k], np.load(tmp_path / "s2" / f"{k}.npy")) for k in got)  # fixed sample
+    rows = [int(np.flatnonzero((logits.numpy() == r).all(1))[0]) for r in got["logits"]]
+    assert rows == sorted(rows) and len(rows) == got["features"].shape[0] == got["labels"].shape[0]
+    assert np.array_equal(got["features"], feats.float().numpy()[rows]) and np.array_equal(got["labels"], labels.numpy()[rows])
