@@ -1,8 +1,36 @@
-// block16_c64_kernel: the fused layer1 BasicBlock of block_c64.h (x ring -> conv1 -> I ring -> conv2 + shortcut, two teams of
-// four waves walking down a strip of 14 columns; read that header first) on v_mfma_f32_16x16x32 (round 4).  Included by
-// conv_igemm.h after halo16.h (Asm16, lds_read16, wait_lgkmcnt, permlane16_swap, perm16).
+// block16_c64_kernel: the layer1 BasicBlock (56x56, 64 -> 64 -> 64 channels) in ONE kernel (gfx950), included by conv_igemm.h
+// after halo16.h (Asm16, lds_read16, wait_lgkmcnt, permlane16_swap, perm16):
+//     out = relu(conv2(relu(conv1(x) + b1)) + b2 + x)
+// The two 3x3 convolutions of a layer1 block are HBM-bound when launched separately (each streams a
+// 200 MB activation in and out per 512 patches, conv2 a second one for the shortcut: 4.5 - 5 TB/s measured);
+// here the intermediate map never leaves the CU, so a block costs one read of x and one write of out.
 //
-// What changes with the MFMA shape:
+//   * ONE 8-wave workgroup per CU walks DOWN a strip of 14 output columns (4 strips per image): x rows
+//     arrive by LDS-DMA into a ring of rows (18 columns = 14 + a halo of 2 on each side), team A (waves 0-3)
+//     turns them into rows of the intermediate map I = relu(conv1(x) + b1) (16 columns = 14 + 1 + 1), rounded to
+//     T exactly as the unfused path stores it, in a second ring; team B (waves 4-7) follows ten rows behind
+//     and turns I rows into output rows.  Nothing is computed twice in y; in x conv1 computes 16 columns for
+//     14 and conv2 uses 14 of its 16 lanes: 1.14x the MFMAs of the unfused pair.
+//   * every lane keeps ITS weight fragments of ITS convolution in registers (36 fragments = 144 VGPRs: wave =
+//     (team, channel half, sub-tile half)), so LDS serves only activation fragments, one ds_read_b128 per MFMA;
+//     the two waves of a SIMD are one A wave and one B wave.
+//   * a step = 8 rows: A computes I rows 8m .. 8m+7 of its strip (4 sub-tiles of 2 rows x 16 columns, two per
+//     wave) while B computes output rows 8m-10 .. 8m-3 (at m = 1 the three sub-tiles that exist, at the step
+//     after the strip's last one the five that remain -- A is then already in the next strip).  ONE workgroup
+//     barrier per step.
+//   * rings: row L = y + 1 of a strip (L = 0 and 57 are the zero rows above and below the image) lives at ring
+//     row L mod 30, and L = 30, 31 ALSO at rows 30, 31, so the 4 rows a sub-tile's window reads (start row even)
+//     are always contiguous: window base + immediate offsets, no wrap inside the loop.  Every strip starts at
+//     ring row 0 again; with 30 rows neither A's writes nor the DMA of the rows two steps ahead (or of the next
+//     strip's first rows) ever meet a row that B or A still reads (DESIGN.md has the table).
+//   * bank conflicts: 16-byte chunk c of the pixel in column j sits at chunk c ^ ((j >> 1) & 7); a ds_read_b128
+//     lane group is 16 consecutive columns of one row = 16 distinct 16-byte bank groups.  The DMA applies the
+//     swizzle on the source side (LDS-DMA writes lane-linear).  x pixels outside the image are zero-filled by
+//     the buffer range check; I columns outside the image are written as zeros.
+//   * shortcut: the x pixels a B wave adds are fetched by LDS-DMA (L2 hits: the rows went through the x ring one
+//     step earlier) into per-wave staging at the start of the step.
+//
+// On v_mfma_f32_16x16x32 (round 4; round 3's 32x32x16 form of this design was removed), against that form:
 //   * a sub-tile is ONE row of 16 columns (was two rows): a wave's step = 4 rows x 16 columns x 32 channels = 4 x 2
 //     accumulators of 4 registers (32, as before).  Lane (n, g): column perm16(n) of the row, k-group g; D gives it channels
 //     16 t + 4 g .. + 3 of that pixel.
@@ -21,6 +49,20 @@
 #pragma once
 
 namespace hipac {
+
+typedef __attribute__((ext_vector_type(2))) short s16x2;
+// ReLU on a dword of two T (bf16 | fp16): the sign bit decides, so it is a packed signed-integer max with 0
+// (== rounding the fp32 ReLU: rounding keeps the sign, -0 becomes +0)
+__device__ __forceinline__ unsigned relu_pk(unsigned v) {
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), s16x2{0, 0}));
+}
+
+constexpr int kBlkRing = 30;              // ring rows (rows 30, 31 of each buffer repeat L = 30, 31)
+constexpr int kBlkXPitch = 18 * 128;      // x ring: 18 columns x 64 channels
+constexpr int kBlkIPitch = 16 * 128;      // I ring: 16 columns
+constexpr int kBlkXBytes = 32 * kBlkXPitch + 512;   // + 4 slots: the last 8-slot DMA piece of a 2-row group overshoots
+constexpr int kBlkIBytes = 32 * kBlkIPitch + 256;   // + 2 slots: idle lanes (columns 14, 15) read 2 pixels past their row
+constexpr int kBlkRsBytes = 2 * 6144 + 2 * 4096;    // shortcut staging: 3 sub-tiles for the mh = 0 B waves, 2 for mh = 1
 
 #ifndef HIPAC_BLK16_AHEAD
 #define HIPAC_BLK16_AHEAD 1
@@ -113,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void block16_c64_kernel(const T* __restrict
 
   const rsrc_t x_rsrc = make_rsrc(in, n_img * (H * W * C * 2));
 
-  // ---- x ring DMA (team A): exactly block_c64.h's (lane-linear 1 KB pieces; nothing depends on the MFMA shape)
+  // ---- x ring DMA (team A): lane-linear 1 KB pieces
   constexpr int NKP = 5;
   int relo[NKP];
 #pragma unroll
@@ -205,7 +247,7 @@ __global__ __launch_bounds__(512, 2) void block16_c64_kernel(const T* __restrict
       permlane16_swap(P[0][0], P[1][0]);
       permlane16_swap(P[0][1], P[1][1]);
       char* const dst = reinterpret_cast<char*>(out) + ((size_t)(unsigned)(pix0 + (y0 + rho) * W) << 7) + out_lane;
-      if (lx < 14) store16_out<HIPAC_NT_STORES != 0>(dst, u32x4{P[0][0], P[0][1], P[1][0], P[1][1]});
+      if (lx < 14) store16_out(dst, u32x4{P[0][0], P[0][1], P[1][0], P[1][1]});
     }
   };
   int pend_pix = 0, pend_sl = 0;

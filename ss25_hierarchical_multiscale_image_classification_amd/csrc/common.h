@@ -17,32 +17,9 @@ typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-#ifndef HIPAC_NT_STORES
-#define HIPAC_NT_STORES 0  // 1: the conv epilogues of the big early maps (layer1's fused block, layer2's convs) store their activations
-                           // non-temporally (streamed past the L2's LRU).  Measured (bf16): the ops timed ALONE get faster (layer2 160 / 218 /
-                           // 193 / 227 -> 146 / 205 / 187 / 202 ns per patch; layers 3-4 2-5 % slower, the fp16q8 kernels +-0), but the whole
-                           // forward gets 0.5 % SLOWER (318.9 k vs 320.6 k patches/s, three alternating runs on one box): inside the
-                           // pipeline the next kernel finds part of a 100-200 MB map still in the L2 / infinity cache, which a per-op
-                           // loop that never reads its output cannot show.  Left off.
-#endif
-// 16-byte activation store of a conv epilogue
-#ifndef HIPAC_WT_STORES
-#define HIPAC_WT_STORES 0  // developer experiment: 1 = `sc1` (write-through: the line goes to memory at once and stays valid in the L2), 2 = `sc0 sc1`, 3 = `nt sc1`.
-                           // Whole forward, alternating runs on one box: 312.9 k plain, 312.1 / 312.0 / 313.0 k -- no policy moves it
-#endif
-template <bool NT>
-__device__ __forceinline__ void store16_out(void* p, u32x4 v) {
-#if HIPAC_WT_STORES == 1
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#elif HIPAC_WT_STORES == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#elif HIPAC_WT_STORES == 3
-  asm volatile("global_store_dwordx4 %0, %1, off nt sc1" ::"v"(p), "v"(v) : "memory");
-#else
-  if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
-  else *reinterpret_cast<u32x4*>(p) = v;
-#endif
-}
+// 16-byte activation store of a conv epilogue.  A plain store: non-temporal and write-through policies measured no faster for
+// the whole forward ("Removed alternatives")
+__device__ __forceinline__ void store16_out(void* p, u32x4 v) { *reinterpret_cast<u32x4*>(p) = v; }
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
@@ -196,8 +173,6 @@ int launch_head(const float* last, int n, const float* fc_w, const float* fc_b, 
                 float* feats, float* logits, int64_t* labels, hipStream_t s);
 int launch_head_pool(const float* part, int n, const float* fc_w, const float* fc_b, int num_classes,
                      float* feats, float* logits, int64_t* labels, hipStream_t s);
-bool x3_on_halo16();  // conv_f16x3.hip: does fp16x3 run on halo16x2.h (weight rows [whi | wlo] per chunk) or on the round-3 SPLIT kernels?
-bool halo_pool_compiled();  // conv_bf16.hip: was the 16x16x32 halo kernel with the direct epilogue compiled in?
 int launch_tap_export(const void* src, int is_f32, int precision, int n, int C, int H, int W, float* dst,
                       hipStream_t s);
 

@@ -4,6 +4,6 @@
 namespace hipac {
 int run_trunk_f16q8(const Net& net, const Plan& p, char* ws, const void* xin, int n_early, int img_off, int n_late,
                     hipStream_t s, int first, int last) {
-  return run_trunk<_Float16, true, 1>(net, p, ws, xin, n_early, img_off, n_late, s, first, last);
+  return run_trunk<_Float16, 1>(net, p, ws, xin, n_early, img_off, n_late, s, first, last);
 }
 }  // namespace hipac

@@ -295,17 +295,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 // activation tile x projection weights) into a second accumulator set and leaves through a
 // second epilogue (bias only, no ReLU) into `outp_p`: one launch, one pass over the input.
 //
-// SPLIT (precision fp16x3, the mode that meets the reference's fp32 results to 1e-3): every value is the PAIR
-// hi = rn16(v), lo = rn16(v - hi) of fp16 numbers.  Activations are stored [pixel][hi: CIN | lo: CIN] (2 CIN
-// elements per pixel), weights [Cout][tap][3 CIN] as per-64-channel triples (hi_c | lo_c | hi_c), and the GEMM
-// runs over 3 CIN "virtual" channels: virtual chunk v = 3c + j reads activation chunk c of the hi plane (j = 0, 1)
-// or of the lo plane (j = 2): D = Whi Xhi + Wlo Xhi + Whi Xlo on v_mfma_f32_32x32x16_f16 with fp32 accumulation
-// (the dropped lo x lo term is 2^-22 relative).  The epilogue splits its fp32 result into a pair again.
-template <bool SPLIT, int CC>
-__device__ __forceinline__ constexpr int split_achunk(int v) {  // activation chunk (in units of 64 channels) of virtual chunk v
-  return SPLIT ? ((v % 3 == 2) ? CC + v / 3 : v / 3) : v;
-}
-// fp32 -> (hi, lo) pair of fp16 fragments
+// fp32 -> (hi, lo) pair of fp16 fragments (the pair layout of precision fp16x3: hi = rn16(v), lo = rn16(v - hi))
 __device__ __forceinline__ void split_pair8(const float* v, f16x8& hi, f16x8& lo) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -313,17 +303,10 @@ __device__ __forceinline__ void split_pair8(const float* v, f16x8& hi, f16x8& lo
     lo[e] = (_Float16)(v[e] - (float)hi[e]);
   }
 }
-__device__ __forceinline__ void split_pair4(const float* v, f16x4& hi, f16x4& lo) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    hi[e] = (_Float16)v[e];
-    lo[e] = (_Float16)(v[e] - (float)hi[e]);
-  }
-}
 
 template <typename T, int CIN, int COUT, int HI, int WI, int KS, int STRIDE, int BM, int BN, int NSTAGE,
-          bool RELU, bool RESID, bool OUTF32, bool PROJ = false, bool SPLIT = false, int WTM = 64, int TKH = 0, int TKW = 0, int UPS = 0>
-__global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kernel(
+          bool RELU, bool RESID, bool OUTF32, bool PROJ = false, int TKH = 0, int TKW = 0, int UPS = 0>
+__global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 2) void conv_glds_kernel(
     const T* __restrict__ in, const T* __restrict__ wgt, const float* __restrict__ bias,
     const T* __restrict__ resid, void* __restrict__ outp, int M, int n_mtiles, const char* __restrict__ zero_page,
     const T* __restrict__ wgt_p = nullptr, const float* __restrict__ bias_p = nullptr,
@@ -338,25 +321,20 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
   constexpr int PAD = UPS ? 0 : KS / 2;
   constexpr int HO = UPS ? HI : (HI + 2 * PAD - KS) / STRIDE + 1;
   constexpr int WO = UPS ? WI : (WI + 2 * PAD - KS) / STRIDE + 1;
-  static_assert(!UPS || (STRIDE == 1 && TKH >= 1 && TKW >= 1 && !PROJ && !RESID && !OUTF32 && !SPLIT), "parity-class data gradient");
-  constexpr int RC = CIN / 64;                      // real 64-channel chunks
-  constexpr int CC = SPLIT ? 3 * RC : RC;           // (virtual) chunks of the K loop
-  constexpr int PIXC = SPLIT ? 2 * CIN : CIN;       // activation elements per input pixel
-  constexpr int OPIX = SPLIT ? 2 * COUT : COUT;     // elements per output pixel (T outputs)
+  static_assert(!UPS || (STRIDE == 1 && TKH >= 1 && TKW >= 1 && !PROJ && !RESID && !OUTF32), "parity-class data gradient");
+  constexpr int CC = CIN / 64;                      // 64-channel chunks of the K loop
   constexpr int KT = KH * KW * CC;
   constexpr int KTOT = KT * 64;
   constexpr int KTP = PROJ ? KT + CC : KT;          // + the projection's K tiles
   static_assert(!PROJ || (KS == 3 && STRIDE == 2 && !RESID && !OUTF32), "projection rides on 3x3/2 only");
-  static_assert(!SPLIT || (std::is_same<T, _Float16>::value && !RESID), "split pairs are fp16");
-  static_assert(WTM == 64 || WTM == 128, "wave tile: 64 or 128 pixels x 64 channels");
-  constexpr int MT = WTM / 32;                     // 32-pixel sub-tiles per wave (4: 0.75 LDS fragment reads per MFMA instead of 1)
-  constexpr int WM = BM / WTM, WN = BN / 64, NWAVES = WM * WN;
+  constexpr int MT = 2;                            // 32-pixel sub-tiles per wave
+  constexpr int WM = BM / 64, WN = BN / 64, NWAVES = WM * WN;
   constexpr int APW = BM / 8 / NWAVES;  // 1-KiB A pieces per wave per K tile
   constexpr int WPW = BN / 8 / NWAVES;  // 1-KiB W pieces per wave per K tile
   constexpr int PPW = APW + WPW;
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int NTILES_N = COUT / BN;
-  static_assert(BM % WTM == 0 && BN % 64 == 0 && COUT % BN == 0 && CIN % 64 == 0, "tile shape");
+  static_assert(BM % 64 == 0 && BN % 64 == 0 && COUT % BN == 0 && CIN % 64 == 0, "tile shape");
   static_assert((BM / 8) % NWAVES == 0 && (BN / 8) % NWAVES == 0, "piece split");
   static_assert(NSTAGE >= 2 && NSTAGE * STAGE <= 160 * 1024, "LDS ring");
   static_assert((NSTAGE - 1) * PPW < 64, "vmcnt range");
@@ -393,7 +371,7 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
     const int rem = mm - b * (HO * WO);
     const int oh = rem / WO, ow = rem - oh * WO;
     const int ih0 = oh * STRIDE - PAD, iw0 = ow * STRIDE - PAD;
-    a_off[i] = (((b * HI + ih0) * WI + iw0) * PIXC + schunk * 8) * 2;
+    a_off[i] = (((b * HI + ih0) * WI + iw0) * CIN + schunk * 8) * 2;
     unsigned mask = 0;
 #pragma unroll
     for (int kh = 0; kh < KH; ++kh)
@@ -420,7 +398,7 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
   using lptr_t = __attribute__((address_space(3))) void*;
   // LDS-DMA through buffer descriptors: a tap that leaves the image (or a row beyond M) gets an offset
   // past the descriptor's range and reads as zeros -- no zero-page select, no 64-bit address arithmetic
-  const rsrc_t in_rsrc = make_rsrc(in_b, (M / (HO * WO)) * (HI * WI * PIXC * 2));
+  const rsrc_t in_rsrc = make_rsrc(in_b, (M / (HO * WO)) * (HI * WI * CIN * 2));
   const rsrc_t w_rsrc = make_rsrc(w_b, COUT * KTOT * 2);
   const rsrc_t wp_rsrc = make_rsrc(PROJ ? wp_b : w_b, COUT * CC * 64 * 2);
   auto issue = [&](int tap, int tapoff_bytes, int kofs_bytes, int stage, bool proj) {
@@ -442,7 +420,7 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
   int rd[4];
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) rd[kk] = r * 128 + (((2 * kk + h) ^ sw) << 4);
-  const int a_rd0 = wm * WTM * 128;
+  const int a_rd0 = wm * 64 * 128;
   const int w_rd0 = BM * 128 + wn * 64 * 128;
 
   f32x16 acc[MT][2], accp[PROJ ? MT : 1][PROJ ? 2 : 1];
@@ -461,10 +439,10 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
   auto issue_next = [&]() __attribute__((always_inline)) {
     if (PROJ && i_t >= KT) {  // centre tap (1,1), channel chunk i_t - KT, projection weights
       const int pc = i_t - KT;
-      issue(4, ((WI + 1) * PIXC + split_achunk<SPLIT, RC>(pc) * 64) * 2, pc * 128, i_t % NSTAGE, true);
+      issue(4, ((WI + 1) * CIN + pc * 64) * 2, pc * 128, i_t % NSTAGE, true);
     } else {
       const int tap = i_kh * KW + i_kw;
-      issue(tap, ((i_kh * WI + i_kw) * PIXC + split_achunk<SPLIT, RC>(i_cc) * 64) * 2, i_t * 128, i_t % NSTAGE, false);
+      issue(tap, ((i_kh * WI + i_kw) * CIN + i_cc * 64) * 2, i_t * 128, i_t % NSTAGE, false);
       if (++i_cc == CC) {
         i_cc = 0;
         if (++i_kw == KW) {
@@ -535,7 +513,7 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
   if constexpr (PROJ) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
-      const int m = m0 + wm * WTM + i * 32 + r;
+      const int m = m0 + wm * 64 + i * 32 + r;
       if (m >= M) continue;
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -545,19 +523,12 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
           const float4 bv = *reinterpret_cast<const float4*>(bias_p + c0);
           const float pv[4] = {accp[i][j][4 * q + 0] + bv.x, accp[i][j][4 * q + 1] + bv.y, accp[i][j][4 * q + 2] + bv.z,
                                accp[i][j][4 * q + 3] + bv.w};
-          if constexpr (SPLIT) {
-            f16x4 oh, ol;
-            split_pair4(pv, oh, ol);
-            *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(outp_p) + (size_t)m * OPIX + c0) = oh;
-            *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(outp_p) + (size_t)m * OPIX + COUT + c0) = ol;
-          } else {
-            typename E::vec4 ov;
-            ov[0] = (T)pv[0];
-            ov[1] = (T)pv[1];
-            ov[2] = (T)pv[2];
-            ov[3] = (T)pv[3];
-            *reinterpret_cast<typename E::vec4*>(reinterpret_cast<T*>(outp_p) + (size_t)m * COUT + c0) = ov;
-          }
+          typename E::vec4 ov;
+          ov[0] = (T)pv[0];
+          ov[1] = (T)pv[1];
+          ov[2] = (T)pv[2];
+          ov[3] = (T)pv[3];
+          *reinterpret_cast<typename E::vec4*>(reinterpret_cast<T*>(outp_p) + (size_t)m * COUT + c0) = ov;
         }
     }
   }
@@ -565,7 +536,7 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
   // ---- epilogue: +bias (+residual) (ReLU) -> NHWC store ---------------------------------
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    const int m = m0 + wm * WTM + i * 32 + r;
+    const int m = m0 + wm * 64 + i * 32 + r;
     if (m >= M) continue;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -597,12 +568,6 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
         }
         if constexpr (OUTF32) {
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(outp) + o) = make_float4(v0, v1, v2, v3);
-        } else if constexpr (SPLIT) {
-          const float sv[4] = {v0, v1, v2, v3};
-          f16x4 oh, ol;
-          split_pair4(sv, oh, ol);
-          *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(outp) + (size_t)m * OPIX + c0) = oh;
-          *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(outp) + (size_t)m * OPIX + COUT + c0) = ol;
         } else {
           typename E::vec4 ov;
           ov[0] = (T)v0;
@@ -617,13 +582,13 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
 }
 
 // ---------------------------------------------------------------------------------------
-// v3: halo direct convolution for the 3x3 / stride 1 / pad 1 layers (13 of the 20 convs,
-// 83 % of the FLOPs).  The v2 kernel re-stages the activation tile once per filter tap
-// (9x the input through L2 -> LDS, which is what bounds it at ~11 TB/s); here a workgroup
-// brings the input rows its BM output pixels need -- a band of zero-padded rows, 64
-// channels deep -- into LDS ONCE per 64-channel chunk and all 9 taps read it at shifted
-// pixel offsets.  Only the weight tile (BN x 64 channels per tap) still streams, through a
-// 2-slot LDS-DMA ring one tap ahead of the MFMAs.
+// Halo direct convolution for the 3x3 / stride 1 / pad 1 layers (13 of the 20 convs, 83 % of
+// the FLOPs; the kernels are in halo16.h and halo16x2.h).  The v2 kernel re-stages the
+// activation tile once per filter tap (9x the input through L2 -> LDS, which is what bounds it
+// at ~11 TB/s); here a workgroup brings the input rows its BM output pixels need -- a band of
+// zero-padded rows, 64 channels deep -- into LDS ONCE per 64-channel chunk and all 9 taps read
+// it at shifted pixel offsets.  Only the weight tile (BN x 64 channels per tap) still streams,
+// through an LDS-DMA ring one tap ahead of the MFMAs.
 //
 // Geometry: NHWC activations flattened over (image, row, col) are one pixel array m; tap
 // (kh,kw) of output pixel m reads pixel m + (kh-1)*W + (kw-1) unless that falls outside the
@@ -636,6 +601,12 @@ __global__ __launch_bounds__((BM / WTM) * (BN / 64) * 64, 2) void conv_glds_kern
 // reads the zero slot of its own parity at its own swizzled chunk, which keeps that property
 // (measured before this: 21-29 % of LDS cycles lost to bank conflicts from a single zero slot).
 // No per-piece div/mod, no pad rows: BM + 2W + 2 pixels per band.
+//
+// PCIN > 0 (second conv of a down-sampling BasicBlock): the block's 1x1 / stride 2 projection shortcut is folded in as
+// PCIN / 64 extra K steps -- the "band" of such a step is a GATHER of the block input's pixels (2y, 2x), 64 channels
+// each, placed where the centre tap reads, the weight tile comes from the projection's [COUT][PCIN] matrix, and `bias`
+// is the sum of both biases: conv2 + projection accumulate in ONE fp32 accumulator, the shortcut map (one HBM round
+// trip) and the projection launch disappear.  `resid` is then the block input [n][2H][2W][PCIN], `wgt_p` the projection.
 // ---------------------------------------------------------------------------------------
 #ifdef HIPAC_HALO_STAMPS
 // developer build: per-phase cycle totals of the halo kernel (s_memtime), summed over workgroups
@@ -647,628 +618,22 @@ static __device__ unsigned long long g_halo_stamps[8];
 #ifndef HIPAC_C64_PF
 #define HIPAC_C64_PF 2  // layer1 kernel: LDS fragment reads run this many k16 steps ahead of their MFMAs
 #endif
-// order of the 36 (tap, k16) steps of a 3x3 x 64-channel accumulation, shared by conv3x3_c64_kernel and the fused block
-// (their results are compared bit for bit): 0 = (kh, kw, k16 step), the default; 1 = (kh, k16 step, kw), what the fragment-sharing
-// experiment of block_c64.h (HIPAC_BLK_SHARE) needs
-#ifndef HIPAC_C64_ORDER
-#define HIPAC_C64_ORDER 0
-#endif
+// order of the 36 (tap, k16) steps of a 3x3 x 64-channel accumulation: (kh, kw, k16 step)
 constexpr int c64_step_kh(int st) { return st / 12; }
-constexpr int c64_step_kw(int st) { return HIPAC_C64_ORDER ? st % 3 : (st % 12) / 4; }
-constexpr int c64_step_kk(int st) { return HIPAC_C64_ORDER ? (st % 12) / 3 : st % 4; }
+constexpr int c64_step_kw(int st) { return (st % 12) / 4; }
+constexpr int c64_step_kk(int st) { return st % 4; }
 
 #ifndef HIPAC_HALO_TAP_UNROLL
 #define HIPAC_HALO_TAP_UNROLL 3  // taps per unrolled group: 3 makes kw a constant (9 is slower: 2x, code size)
 #endif
-#ifndef HIPAC_HALO_W_ISSUE_KK
-#define HIPAC_HALO_W_ISSUE_KK 1  // k16 sub-step after whose MFMAs the next weight tile is requested (-1: step start)
-#endif
 #ifndef HIPAC_HALO_GRID
 #define HIPAC_HALO_GRID 512  // persistent halo workgroups: 2 per CU x 256 CUs
 #endif
-#ifndef HIPAC_HALO_DIRECT_EPI
-#define HIPAC_HALO_DIRECT_EPI 0  // 1: epilogue straight from the accumulators (v_permlane32_swap pairs the lane halves), no LDS
-                                 // staging.  Bit-identical; measured NOT faster (trunk 3.65 vs 3.59 us per patch): the epilogue
-                                 // shrinks 13 k -> 8.6 k cycles without a residual, but 32-byte runs per pixel make the residual
-                                 // reads and the stores slower than the staged form's full 128-byte lines
-#endif
 constexpr int halo_band_pieces(int W, int BM) { return (BM + 2 * W + 2 + 2 + 7) / 8; }  // 8-pixel (1 KB) pieces
-
-// NSW = depth of the weight ring (2, or 3 where LDS leaves room for two workgroups per CU).
-// Epilogue: every wave sends its 32-pixel sub-tiles through a private fp32 staging area in LDS so
-// that global traffic is 16-byte items of contiguous channel runs (residual loads and stores)
-// with no workgroup barrier; workgroups are persistent and the next tile's band is prefetched
-// behind the epilogue.
-// SPLIT: fp16 (hi, lo) pairs, see conv_glds_kernel; virtual chunk 3c + 1 (Wlo x Xhi) reuses the band of 3c.
-// WM_ x WN_ = the 4 waves as pixel parts x channel parts; MINW = waves per SIMD the register budget is set for (1: one
-// 512-register wave per SIMD with a 128 x 128 tile -- 0.5 LDS fragment reads per MFMA instead of 0.75).
-// PCIN > 0 (second conv of a down-sampling BasicBlock): the block's 1x1 / stride 2 projection shortcut is folded in as
-// PCIN / 64 extra K steps -- the "band" of such a step is a GATHER of the block input's pixels (2y, 2x), 64 channels
-// each, placed where the centre tap reads, the weight tile comes from the projection's [COUT][PCIN] matrix, and `bias`
-// is the sum of both biases: conv2 + projection accumulate in ONE fp32 accumulator, the shortcut map (one HBM round
-// trip) and the projection launch disappear.  `resid` is then the block input [n][2H][2W][PCIN], `wgt_p` the projection.
-// DBLW (SPLIT only, where the LDS budget allows a weight ring of two 2-tile slots): per real 64-channel chunk the K loop runs
-// nine DOUBLE steps -- the band of the hi plane against the weight tiles [Whi | Wlo] of a tap, two MFMAs per activation
-// fragment -- and nine single steps (lo plane x Whi): 18 barriers and (MTW + 2 NT) / (2 MTW NT) fragment reads per MFMA on two
-// thirds of the work instead of 27 barriers and (MTW + NT) / (MTW NT).
-template <typename T, int CIN, int COUT, int H, int W, int BM, int BN, int NSW, bool RELU, bool RESID, bool OUTF32,
-          bool SPLIT = false, int WM_ = 2, int WN_ = 2, int MINW = 2, int PCIN = 0, bool DBLW = false>
-__global__ __launch_bounds__(256, MINW) void conv3x3_halo_kernel(const T* __restrict__ in, const T* __restrict__ wgt,
-                                                              const float* __restrict__ bias,
-                                                              const T* __restrict__ resid, void* __restrict__ outp,
-                                                              int M, int n_img, int n_mtiles,
-                                                              const char* __restrict__ zero_page,
-                                                              const T* __restrict__ wgt_p = nullptr) {
-  using E = Elem<T>;
-  using frag = typename E::frag;
-  constexpr int RC = CIN / 64;                      // real 64-channel chunks
-  constexpr int CC = SPLIT ? 3 * RC : RC;           // (virtual) chunks of the K loop
-  constexpr int VCIN = CC * 64;                     // K elements per tap
-  constexpr int PIXC = SPLIT ? 2 * CIN : CIN;       // activation elements per input pixel
-  constexpr int OPIX = SPLIT ? 2 * COUT : COUT;     // elements per pixel of T-typed outputs and of the residual
-  constexpr int KTOT = 9 * VCIN;
-  static_assert(!SPLIT || std::is_same<T, _Float16>::value, "split pairs are fp16");
-  constexpr int WM = WM_, WN = WN_;                 // 4 waves: pixel parts x channel parts
-  static_assert(WM * WN == 4, "four waves");
-  constexpr int MTW = BM / (WM * 32);               // 32-pixel sub-tiles per wave (2 or 4)
-  constexpr int WTN = BN / WN, NT = WTN / 32;       // channels per wave, 32-wide tiles per wave
-  constexpr int A_PIECES = halo_band_pieces(W, BM);
-  constexpr int A_BYTES = A_PIECES * 1024;
-  constexpr int W_BYTES = BN * 128;
-  constexpr int WPW = BN / 8 / 4;                    // W pieces per wave per tap
-  constexpr int NTILES_N = COUT / BN;
-  constexpr int PCC = PCIN / 64;                    // projection K steps (0: no folded projection)
-  constexpr int NSTEP = 9 * CC + PCC;
-  static_assert(PCIN % 64 == 0 && (PCIN == 0 || (!RESID && !SPLIT)), "folded projection replaces the residual input");
-  static_assert((BM == 128 || BM == 256 || BM == 512) && WTN % 32 == 0 && COUT % BN == 0 && CIN % 64 == 0, "tile shape");
-  static_assert((BN / 8) % 4 == 0, "W piece split");
-  static_assert(NSW == 2 || NSW == 3, "weight ring depth");
-  constexpr int STG_BYTES = 4 * 32 * (WTN * 4 + 16);  // 4 waves x [32 px][WTN fp32 + pad] epilogue staging
-  static_assert(!DBLW || (SPLIT && NSW == 2 && PCIN == 0), "double weight steps: split pairs, two ring slots");
-  constexpr int SLOT_BYTES = DBLW ? 2 * W_BYTES : W_BYTES;  // one ring slot
-  constexpr int S_BYTES = NSW * SLOT_BYTES > STG_BYTES ? NSW * SLOT_BYTES : STG_BYTES;  // ring, aliased by the staging
-  static_assert(A_BYTES + S_BYTES <= 160 * 1024 / MINW, "LDS: MINW workgroups per CU");
-
-  extern __shared__ __attribute__((aligned(1024))) unsigned char ring[];
-  unsigned char* const Abuf = ring;
-  unsigned char* const Wbuf = ring + A_BYTES;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave % WM, wn = wave / WM;
-  const int r = lane & 31, h = lane >> 5;
-
-  using gptr_t = const __attribute__((address_space(1))) void*;
-  using lptr_t = __attribute__((address_space(3))) void*;
-  const char* in_b = reinterpret_cast<const char*>(in);
-  const char* w_b = reinterpret_cast<const char*>(wgt);
-  const int prow = lane >> 3, dchunk = lane & 7;
-
-  // band of the tile starting at pixel m0_: the contiguous pixel range [m0_ - W - 1, mlast_ + W + 1]
-  auto issue_band_of = [&](int m0_, int cc) {
-    const int mlast_ = (m0_ + BM <= M ? m0_ + BM : M) - 1;
-    const int mstart_ = m0_ - W - 1;
-    const int npx_ = mlast_ - m0_ + 1 + 2 * W + 2;  // band pixels; slots 2..npx+1 (slots 0, 1 = zeros)
-    const int npieces_ = (npx_ + 2 + 7) >> 3;
-    for (int p = wave; p < npieces_; p += 4) {
-      const int q = p * 8 + prow;                // slot
-      const int mm = mstart_ + q - 2;            // flattened pixel held by this slot
-      const bool ok = q >= 2 && q <= npx_ + 1 && mm >= 0 && mm < M;
-      const int schunk = dchunk ^ ((q >> 1) & 7);
-      const char* src = ok ? in_b + ((size_t)mm * PIXC + split_achunk<SPLIT, RC>(cc) * 64 + schunk * 8) * 2
-                           : zero_page + dchunk * 16;
-      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Abuf + p * 1024), 16, 0, 0);
-    }
-  };
-
-  // Persistent workgroups: virtual block id vb = blockIdx.x + i * gridDim.x (gridDim.x % 8 == 0, so a
-  // workgroup stays on its XCD's slice of the tile order).  The band of the NEXT tile is brought
-  // in during the epilogue of the current one (the epilogue stages through the weight ring only).
-  for (int vb = blockIdx.x, first_tile = 1;; vb += gridDim.x, first_tile = 0) {
-  const int xcd = vb & 7, slot = vb >> 3;
-  const int mt = (slot / NTILES_N) * 8 + xcd;
-  const int nt = slot % NTILES_N;
-  if (mt >= n_mtiles) break;  // mt grows with vb on a fixed XCD: nothing valid follows
-  const int m0 = mt * BM, n0 = nt * BN;
-  const int mlast = (m0 + BM <= M ? m0 + BM : M) - 1;
-  const int mstart = m0 - W - 1;
-  auto issue_band = [&](int cc) { issue_band_of(m0, cc); };
-  if (!first_tile) __builtin_amdgcn_s_barrier();  // the previous tile's staging reads are done: ring is free
-  int w_off[WPW];
-#pragma unroll
-  for (int i = 0; i < WPW; ++i) {
-    const int row = (wave + 4 * i) * 8 + prow;
-    w_off[i] = ((n0 + row) * KTOT + (dchunk ^ ((row >> 1) & 7)) * 8) * 2;
-  }
-  // weight DMA through a buffer descriptor: per-lane 32-bit row offset in a VGPR (computed once per
-  // tile), the tap / chunk offset in an SGPR -- no per-piece address arithmetic in the tap loop
-  const rsrc_t w_rsrc = make_rsrc(w_b, COUT * KTOT * 2);
-  int wp_off[PCC > 0 ? WPW : 1];
-  if constexpr (PCC > 0) {
-#pragma unroll
-    for (int i = 0; i < WPW; ++i) {
-      const int row = (wave + 4 * i) * 8 + prow;
-      wp_off[i] = ((n0 + row) * PCIN + (dchunk ^ ((row >> 1) & 7)) * 8) * 2;
-    }
-  }
-  const rsrc_t wp_rsrc = make_rsrc(PCC > 0 ? reinterpret_cast<const char*>(wgt_p) : w_b, COUT * (PCC > 0 ? PCIN : KTOT) * 2);
-  auto issue_w = [&](int step, int slot_) {  // weights of step = cc*9 + tap: K offset (tap*CIN + cc*64)
-    if (PCC > 0 && step >= 9 * CC) {  // uniform: a projection step, 64 input channels of the 1x1 matrix
-      const int kofs_bytes = (step - 9 * CC) * 128;
-      static_for<WPW>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        buffer_load_lds16(wp_rsrc, Wbuf + slot_ * W_BYTES + (wave + 4 * i) * 1024, wp_off[PCC > 0 ? i : 0], kofs_bytes);
-      });
-      // (an empty statement hipcc cannot merge: without it the two paths' DMA calls are sunk into one block whose descriptor and
-      // offsets are SELECTED -- the offset arrays then live in scratch and every DMA sits in a waterfall loop behind a vmcnt(0))
-      asm volatile("" ::: "memory");
-      return;
-    }
-    const int cc = step / 9, tap = step - cc * 9;
-    const int kofs_bytes = (tap * VCIN + cc * 64) * 2;
-    static_for<WPW>([&](auto I) {
-      constexpr int i = decltype(I)::value;
-      buffer_load_lds16(w_rsrc, Wbuf + slot_ * W_BYTES + (wave + 4 * i) * 1024, w_off[i], kofs_bytes);
-    });
-  };
-  // folded projection: the block input's pixel (2y, 2x) of every output pixel of the tile, 64 channels of chunk pc, at the
-  // slot the centre tap reads for that output pixel (q0 = m - mstart + 2)
-  auto issue_gather = [&](int pc) {
-    if constexpr (PCC > 0) {
-      const int npx_ = mlast - m0 + 1;
-      const int first = W + 3, last = first + npx_ - 1;  // slots that hold pixels
-      for (int p = wave + (first >> 3); p <= (last >> 3); p += 4) {
-        const int q = p * 8 + prow;
-        const int mm = m0 + q - first;
-        const bool ok = q >= first && q <= last;
-        const int b = mm / (H * W), rem = mm - b * (H * W), y = rem / W, x = rem - y * W;
-        const int schunk = dchunk ^ ((q >> 1) & 7);
-        const char* src = ok ? reinterpret_cast<const char*>(resid) +
-                                   ((((size_t)b * (2 * H) + 2 * y) * (2 * W) + 2 * x) * PCIN + pc * 64 + schunk * 8) * 2
-                             : zero_page + dchunk * 16;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Abuf + p * 1024), 16, 0, 0);
-      }
-    }
-  };
-
-  // ---- consumer side: slot of this lane's two output pixels for tap (0, centre column) ----
-  int q0[MTW];
-  // bit 0: x == 0, bit 1: x == W-1, bit 2: y == 0, bit 3: y == H-1.  One register per sub-tile and one AND
-  // per tap: four bool arrays tested against the runtime (kh, kw) cost 7-13 % of the kernel (compare /
-  // mask-combine chains in the tap loop)
-  int eflags[MTW];
-#pragma unroll
-  for (int i = 0; i < MTW; ++i) {
-    int m = m0 + wm * (MTW * 32) + i * 32 + r;
-    m = m <= mlast ? m : mlast;  // tail lanes read a valid pixel; their results are not stored
-    const int b = m / (H * W);
-    const int rem = m - b * (H * W);
-    const int y = rem / W, x = rem - y * W;
-    q0[i] = m - mstart + 2;                       // tap (kh,kw) -> q0 + (kh-1)*W + kw - 1
-    eflags[i] = (x == 0 ? 1 : 0) | (x == W - 1 ? 2 : 0) | (y == 0 ? 4 : 0) | (y == H - 1 ? 8 : 0);
-  }
-  const int sw_w = (r >> 1) & 7;
-  int rdw[4], ck[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    ck[kk] = (2 * kk + h) << 4;
-    rdw[kk] = (wn * WTN + r) * 128 + (((2 * kk + h) ^ sw_w) << 4);
-  }
-
-  f32x16 acc[MTW][NT];
-#pragma unroll
-  for (int i = 0; i < MTW; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // Epilogue geometry (per WAVE, no workgroup barriers): the wave owns MTW sub-tiles of 32 pixels x
-  // WTN channels.  Sub-tile i goes through the wave's private fp32 staging [32 px][WTN] and leaves
-  // as 16-byte items (8 channels): item = lane + 64k -> pixel item / CPW, channel group lane % CPW.
-  constexpr int CPW = WTN / 8;                      // 8-channel items per pixel (wave's channel half)
-  constexpr int IPT = 32 * CPW / 64;                // items per lane and sub-tile
-  constexpr int SROWW = WTN * 4 + 16;               // staging row: WTN fp32 + pad
-  static_assert(64 % CPW == 0 && (32 * CPW) % 64 == 0, "epilogue items");
-  constexpr bool DIRECT = HIPAC_HALO_DIRECT_EPI && !SPLIT && sizeof(T) == 2 && IPT == 2 * NT;
-  static_assert(4 * 32 * SROWW <= S_BYTES, "per-wave staging fits the ring region");
-  const int e_c0 = n0 + wn * WTN + (lane % CPW) * 8;  // first of this lane's 8 output channels
-  const int e_px = lane / CPW;                        // pixel of item k: e_px + k * (64 / CPW)
-  // residual, prefetched into registers: sub-tile 0 behind the MFMAs of the last K step,
-  // sub-tile i+1 behind the staging of sub-tile i (two register sets)
-  // (SPLIT: the two register sets hold the hi and the lo fragments of ONE sub-tile, fetched at the top of that sub-tile)
-  frag rv[2][RESID ? IPT : 1];
-  auto load_resid = [&](auto SUB) {
-    constexpr int i = decltype(SUB)::value;
-    if constexpr (RESID) {
-#pragma unroll
-      for (int k = 0; k < IPT; ++k) {
-        int m = m0 + wm * (MTW * 32) + i * 32 + e_px + k * (64 / CPW);
-        m = m < M ? m : M - 1;  // unconditional load from a valid row (tail rows are never stored)
-        if constexpr (SPLIT) {
-          rv[0][k] = *reinterpret_cast<const frag*>(resid + (size_t)m * OPIX + e_c0);
-          rv[1][k] = *reinterpret_cast<const frag*>(resid + (size_t)m * OPIX + COUT + e_c0);
-        } else if constexpr (DIRECT) {
-          // item k = (channel tile j, pair qp): this lane's pixel r, the 8 channels it will also store (16 qp + 8 h)
-          int md = m0 + wm * (MTW * 32) + i * 32 + r;
-          md = md < M ? md : M - 1;
-          rv[i & 1][k] = *reinterpret_cast<const frag*>(resid + (size_t)md * COUT + n0 + wn * WTN + (k >> 1) * 32 + 16 * (k & 1) + 8 * h);
-        } else {
-          rv[i & 1][k] = *reinterpret_cast<const frag*>(resid + (size_t)m * COUT + e_c0);
-        }
-      }
-    }
-  };
-
-  HALO_STAMP(t_start);
-#ifdef HIPAC_HALO_STAMPS
-  unsigned long long t_first = 0;
-#endif
-  int s = 0;  // K step counter
-  if constexpr (DBLW) {
-    // ---- double weight steps (see the template note): step = (chunk c, phase, tap), phase 0 = hi plane x [Whi | Wlo]
-    constexpr int NSTEP2 = 18 * RC;
-    auto issue_w2 = [&](int step, int slot_) {
-      const int c = step / 18, rr = step - c * 18, ph = rr >= 9 ? 1 : 0, tap = rr - 9 * ph;
-      const int kofs_bytes = (tap * VCIN + 3 * c * 64) * 2;  // the hi_c block of this tap; lo_c follows 128 bytes on
-      static_for<WPW>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        buffer_load_lds16(w_rsrc, Wbuf + slot_ * SLOT_BYTES + (wave + 4 * i) * 1024, w_off[i], kofs_bytes);
-      });
-      if (ph == 0)
-        static_for<WPW>([&](auto I) {
-          constexpr int i = decltype(I)::value;
-          buffer_load_lds16(w_rsrc, Wbuf + slot_ * SLOT_BYTES + W_BYTES + (wave + 4 * i) * 1024, w_off[i], kofs_bytes + 128);
-        });
-    };
-    if (first_tile) issue_band(0);
-    issue_w2(0, 0);
-    for (int c2 = 0; c2 < 2 * RC; ++c2) {
-      const int ph = c2 & 1;
-      if (c2 > 0) {
-        __builtin_amdgcn_s_barrier();  // every wave has finished reading the previous band
-        issue_band(3 * (c2 >> 1) + 2 * ph);  // virtual chunk 3c = hi plane, 3c + 2 = lo plane
-      }
-#pragma unroll HIPAC_HALO_TAP_UNROLL
-      for (int tap = 0; tap < 9; ++tap, ++s) {
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        const int kh = tap / 3, kw = tap - kh * 3;
-        const int toff = (kh - 1) * W + kw - 1;
-        const unsigned char* wst = Wbuf + (s & 1) * SLOT_BYTES;
-        const int tapmask = (kw == 0 ? 1 : 0) | (kw == 2 ? 2 : 0) | (kh == 0 ? 4 : 0) | (kh == 2 ? 8 : 0);
-        int abase[MTW], asw[MTW];
-#pragma unroll
-        for (int i = 0; i < MTW; ++i) {
-          const bool off_img = (eflags[i] & tapmask) != 0;
-          const int qt = q0[i] + toff;
-          const int q = off_img ? (qt & 1) : qt;
-          abase[i] = q << 7;
-          asw[i] = ((qt >> 1) & 7) << 4;
-        }
-        frag af[2][MTW], wf[2][2 * NT];
-#pragma unroll
-        for (int i = 0; i < MTW; ++i) af[0][i] = *reinterpret_cast<const frag*>(Abuf + abase[i] + (ck[0] ^ asw[i]));
-#pragma unroll
-        for (int j = 0; j < NT; ++j) wf[0][j] = *reinterpret_cast<const frag*>(wst + j * 4096 + rdw[0]);
-        if (ph == 0) {
-#pragma unroll
-          for (int j = 0; j < NT; ++j) wf[0][NT + j] = *reinterpret_cast<const frag*>(wst + W_BYTES + j * 4096 + rdw[0]);
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          if (kk + 1 < 4) {
-#pragma unroll
-            for (int i = 0; i < MTW; ++i)
-              af[(kk + 1) & 1][i] = *reinterpret_cast<const frag*>(Abuf + abase[i] + (ck[kk + 1] ^ asw[i]));
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-              wf[(kk + 1) & 1][j] = *reinterpret_cast<const frag*>(wst + j * 4096 + rdw[kk + 1]);
-            if (ph == 0) {
-#pragma unroll
-              for (int j = 0; j < NT; ++j)
-                wf[(kk + 1) & 1][NT + j] = *reinterpret_cast<const frag*>(wst + W_BYTES + j * 4096 + rdw[kk + 1]);
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < MTW; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = E::mfma(wf[kk & 1][j], af[kk & 1][i], acc[i][j]);
-          if (ph == 0) {
-#pragma unroll
-            for (int i = 0; i < MTW; ++i)
-#pragma unroll
-              for (int j = 0; j < NT; ++j) acc[i][j] = E::mfma(wf[kk & 1][NT + j], af[kk & 1][i], acc[i][j]);
-          }
-          if (kk == 1 && s + 1 < NSTEP2) issue_w2(s + 1, (s + 1) & 1);  // its slot was freed by this step's barrier
-        }
-        __builtin_amdgcn_s_setprio(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-    }
-  } else {
-  if (first_tile) issue_band(0);
-#pragma unroll
-  for (int pstep = 0; pstep < NSW - 1; ++pstep)
-    if (pstep < NSTEP) issue_w(pstep, pstep);
-  for (int cc = 0; cc < CC; ++cc) {
-    if (cc > 0 && (!SPLIT || cc % 3 != 1)) {  // (SPLIT: chunk 3c + 1 multiplies the band of 3c by the low weight halves)
-      __builtin_amdgcn_s_barrier();  // every wave has finished reading the previous chunk's band
-      issue_band(cc);
-    }
-#pragma unroll HIPAC_HALO_TAP_UNROLL
-    for (int tap = 0; tap < 9; ++tap, ++s) {
-      // W(s) must have landed; the band too at tap 0 (it was issued AFTER W(s+1..), so drain everything)
-      if (NSW == 3 && tap != 0 && s + 1 < NSTEP) wait_vmcnt<WPW>();
-      else wait_vmcnt<0>();
-#ifndef HIPAC_ABL_NO_BARRIER
-      __builtin_amdgcn_s_barrier();
-#endif
-#ifdef HIPAC_HALO_STAMPS
-      if (s == 0) {
-        t_first = __builtin_amdgcn_s_memtime();
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-      }
-#endif
-#if !defined(HIPAC_ABL_NO_W_DMA) && HIPAC_HALO_W_ISSUE_KK < 0
-      if (s + NSW - 1 < NSTEP) issue_w(s + NSW - 1, (s + NSW - 1) % NSW);
-#endif
-      if (RESID && !SPLIT && s == NSTEP - 1) load_resid(std::integral_constant<int, 0>{});
-      const int kh = tap / 3, kw = tap - kh * 3;
-      const int toff = (kh - 1) * W + kw - 1;
-      const unsigned char* wst = Wbuf + (s % NSW) * W_BYTES;
-      const int tapmask = (kw == 0 ? 1 : 0) | (kw == 2 ? 2 : 0) | (kh == 0 ? 4 : 0) | (kh == 2 ? 8 : 0);  // uniform
-      int abase[MTW], asw[MTW];
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) {
-        const bool off_img = (eflags[i] & tapmask) != 0;
-        // out-of-image taps read a zero pixel: slot 0 or 1 by the parity of the slot the lane would
-        // have read, at the chunk position its swizzle selects -- i.e. the SAME 16-byte bank group
-        // as the in-image address, so redirected lanes never collide with their neighbours
-        const int qt = q0[i] + toff;
-        const int q = off_img ? (qt & 1) : qt;
-        abase[i] = q << 7;
-        asw[i] = ((qt >> 1) & 7) << 4;
-      }
-      frag af[2][MTW], wf[2][NT];
-#ifdef HIPAC_ABL_NO_LDSREAD
-      {
-        const frag c0 = __builtin_bit_cast(frag, u32x4{(unsigned)abase[0], (unsigned)asw[0], (unsigned)toff, 1u});
-#pragma unroll
-        for (int i = 0; i < MTW; ++i) af[0][i] = af[1][i] = c0;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) wf[0][j] = wf[1][j] = c0;
-        (void)wst;
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-        for (int i = 0; i < MTW; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = E::mfma(wf[kk & 1][j], af[kk & 1][i], acc[i][j]);
-      __builtin_amdgcn_s_setprio(0);
-      continue;
-#endif
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) af[0][i] = *reinterpret_cast<const frag*>(Abuf + abase[i] + (ck[0] ^ asw[i]));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) wf[0][j] = *reinterpret_cast<const frag*>(wst + j * 4096 + rdw[0]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        if (kk + 1 < 4) {
-#pragma unroll
-          for (int i = 0; i < MTW; ++i)
-            af[(kk + 1) & 1][i] = *reinterpret_cast<const frag*>(Abuf + abase[i] + (ck[kk + 1] ^ asw[i]));
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            wf[(kk + 1) & 1][j] = *reinterpret_cast<const frag*>(wst + j * 4096 + rdw[kk + 1]);
-        }
-#pragma unroll
-        for (int i = 0; i < MTW; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = E::mfma(wf[kk & 1][j], af[kk & 1][i], acc[i][j]);
-#if !defined(HIPAC_ABL_NO_W_DMA) && HIPAC_HALO_W_ISSUE_KK >= 0
-        // the next step's weight DMA is issued from inside the MFMA stream (its slot was freed by this
-        // step's barrier), where its issue cost hides behind queued MFMAs instead of delaying the
-        // step's first LDS reads
-        if (kk == HIPAC_HALO_W_ISSUE_KK && s + NSW - 1 < NSTEP) issue_w(s + NSW - 1, (s + NSW - 1) % NSW);
-#endif
-      }
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-  }
-
-  }  // !DBLW
-  if constexpr (PCC > 0) {
-    // ---- the folded projection: PCC more K steps, centre tap only (no image-edge cases: pixel (2y, 2x) always exists)
-    for (int pc = 0; pc < PCC; ++pc, ++s) {
-      __builtin_amdgcn_s_barrier();  // every wave has finished reading the previous band
-      issue_gather(pc);
-      wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      if (s + NSW - 1 < NSTEP) issue_w(s + NSW - 1, (s + NSW - 1) % NSW);
-      const unsigned char* wst = Wbuf + (s % NSW) * W_BYTES;
-      int abase[MTW], asw[MTW];
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) abase[i] = q0[i] << 7, asw[i] = ((q0[i] >> 1) & 7) << 4;
-      frag af[2][MTW], wf[2][NT];
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) af[0][i] = *reinterpret_cast<const frag*>(Abuf + abase[i] + (ck[0] ^ asw[i]));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) wf[0][j] = *reinterpret_cast<const frag*>(wst + j * 4096 + rdw[0]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        if (kk + 1 < 4) {
-#pragma unroll
-          for (int i = 0; i < MTW; ++i)
-            af[(kk + 1) & 1][i] = *reinterpret_cast<const frag*>(Abuf + abase[i] + (ck[kk + 1] ^ asw[i]));
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            wf[(kk + 1) & 1][j] = *reinterpret_cast<const frag*>(wst + j * 4096 + rdw[kk + 1]);
-        }
-#pragma unroll
-        for (int i = 0; i < MTW; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = E::mfma(wf[kk & 1][j], af[kk & 1][i], acc[i][j]);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-  }
-
-  HALO_STAMP(t_loop);
-  // ---- epilogue -------------------------------------------------------------------------------
-  const float4 b_lo = *reinterpret_cast<const float4*>(bias + e_c0);
-  const float4 b_hi = *reinterpret_cast<const float4*>(bias + e_c0 + 4);
-  __builtin_amdgcn_s_barrier();  // every wave has left the K loop: band and ring are free
-  {
-    // prefetch the next tile's first band chunk; it lands behind this epilogue
-    const int vn = vb + gridDim.x;
-    const int mtn = ((vn >> 3) / NTILES_N) * 8 + (vn & 7);
-    if (mtn < n_mtiles) issue_band_of(mtn * BM, 0);
-  }
-  unsigned char* const Sl = Wbuf + wave * (32 * SROWW);  // this wave's private staging
-  if constexpr (DIRECT) {
-    // Straight from the accumulators: lane (r, h) holds pixel r of the sub-tile, channels 8q + 4h .. +3 of every 32-wide
-    // tile.  Bias, residual, ReLU and the rounding happen there; one v_permlane32_swap per packed dword then pairs the
-    // lane halves so that every lane stores 16 contiguous bytes (channels 16 qp + 8 h .. +7) -- no LDS round trip, no
-    // waits between sub-tiles.  The residual arrives in the stored layout and is un-paired by the same swap.  Same
-    // additions in the same order as the staged form: bit-identical results.
-    float4 bv[NT][4];
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bv[j][q] = *reinterpret_cast<const float4*>(bias + n0 + wn * WTN + j * 32 + 8 * q + 4 * h);
-    static_for<MTW>([&](auto SUB) {
-      constexpr int i = decltype(SUB)::value;
-      if constexpr (i + 1 < MTW) load_resid(std::integral_constant<int, i + 1>{});
-      const int m = m0 + wm * (MTW * 32) + i * 32 + r;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        unsigned P[4][2];
-#pragma unroll
-        for (int qp = 0; qp < 2; ++qp) {
-          unsigned rd[4] = {0u, 0u, 0u, 0u};
-          if constexpr (RESID) {
-            const u32x4 t = __builtin_bit_cast(u32x4, rv[i & 1][2 * j + qp]);
-            rd[0] = t[0], rd[1] = t[1], rd[2] = t[2], rd[3] = t[3];
-            permlane32_swap(rd[0], rd[2]);  // -> (rd[0], rd[1]) = channels of q = 2 qp, (rd[2], rd[3]) = those of q = 2 qp + 1
-            permlane32_swap(rd[1], rd[3]);
-          }
-#pragma unroll
-          for (int qq = 0; qq < 2; ++qq) {
-            const int q = 2 * qp + qq;
-            float v0 = acc[i][j][4 * q + 0] + bv[j][q].x, v1 = acc[i][j][4 * q + 1] + bv[j][q].y;
-            float v2 = acc[i][j][4 * q + 2] + bv[j][q].z, v3 = acc[i][j][4 * q + 3] + bv[j][q].w;
-            if constexpr (RESID) {
-              const typename E::vec4 rr = __builtin_bit_cast(typename E::vec4, u32x2{rd[2 * qq], rd[2 * qq + 1]});
-              v0 += (float)rr[0], v1 += (float)rr[1], v2 += (float)rr[2], v3 += (float)rr[3];
-            }
-            if constexpr (RELU) v0 = fmaxf(v0, 0.f), v1 = fmaxf(v1, 0.f), v2 = fmaxf(v2, 0.f), v3 = fmaxf(v3, 0.f);
-            if constexpr (OUTF32) {
-              if (m < M)
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(outp) + (size_t)m * COUT + n0 + wn * WTN + j * 32 + 8 * q + 4 * h) =
-                    make_float4(v0, v1, v2, v3);
-            } else {
-              P[q][0] = PackPair<T>::pack_rn(v0, v1);
-              P[q][1] = PackPair<T>::pack_rn(v2, v3);
-            }
-          }
-          if constexpr (!OUTF32) {
-            permlane32_swap(P[2 * qp][0], P[2 * qp + 1][0]);
-            permlane32_swap(P[2 * qp][1], P[2 * qp + 1][1]);
-            if (m < M)
-              *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(outp) + (size_t)m * COUT + n0 + wn * WTN + j * 32 + 16 * qp + 8 * h) =
-                  u32x4{P[2 * qp][0], P[2 * qp][1], P[2 * qp + 1][0], P[2 * qp + 1][1]};
-          }
-        }
-      }
-    });
-  } else
-  static_for<MTW>([&](auto SUB) {
-    constexpr int i = decltype(SUB)::value;
-    if constexpr (SPLIT) {
-      load_resid(std::integral_constant<int, i>{});  // lands behind the staging round trip below
-    } else if constexpr (i + 1 < MTW) {
-      load_resid(std::integral_constant<int, i + 1>{});
-    }
-    // accumulators -> fp32 rows (LDS operations of one wave complete in order: no barrier)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 v;
-        v[0] = acc[i][j][4 * q + 0];
-        v[1] = acc[i][j][4 * q + 1];
-        v[2] = acc[i][j][4 * q + 2];
-        v[3] = acc[i][j][4 * q + 3];
-        *reinterpret_cast<f32x4*>(Sl + r * SROWW + (j * 32 + 8 * q + 4 * h) * 4) = v;
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-      const int px = e_px + k * (64 / CPW);
-      const int m = m0 + wm * (MTW * 32) + i * 32 + px;
-      const f32x4 lo = *reinterpret_cast<const f32x4*>(Sl + px * SROWW + (lane % CPW) * 32);
-      const f32x4 hi = *reinterpret_cast<const f32x4*>(Sl + px * SROWW + (lane % CPW) * 32 + 16);
-      if (m < M) {
-        float v[8] = {lo[0] + b_lo.x, lo[1] + b_lo.y, lo[2] + b_lo.z, lo[3] + b_lo.w,
-                      hi[0] + b_hi.x, hi[1] + b_hi.y, hi[2] + b_hi.z, hi[3] + b_hi.w};
-        const size_t o = (size_t)m * COUT + e_c0;
-        if constexpr (RESID && SPLIT) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += (float)rv[0][k][e] + (float)rv[1][k][e];  // hi + lo is exact in fp32
-        } else if constexpr (RESID) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += (float)rv[i & 1][k][e];
-        }
-        if constexpr (RELU) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if constexpr (OUTF32) {
-          float* op = reinterpret_cast<float*>(outp) + o;
-          *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
-          *reinterpret_cast<float4*>(op + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        } else if constexpr (SPLIT) {
-          f16x8 oh, ol;
-          split_pair8(v, oh, ol);
-          _Float16* op = reinterpret_cast<_Float16*>(outp) + (size_t)m * OPIX + e_c0;
-          *reinterpret_cast<f16x8*>(op) = oh;
-          *reinterpret_cast<f16x8*>(op + COUT) = ol;
-        } else {
-          frag ov;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ov[e] = (T)v[e];
-          *reinterpret_cast<frag*>(reinterpret_cast<T*>(outp) + o) = ov;
-        }
-      }
-    }
-    // the next sub-tile overwrites the staging rows: this wave's reads above must have returned
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  });
-#ifdef HIPAC_HALO_STAMPS
-  HALO_STAMP(t_end);
-  if (tid == 0) {
-    atomicAdd(&g_halo_stamps[0], t_first - t_start);  // prologue: band + first weight tile in flight
-    atomicAdd(&g_halo_stamps[1], t_loop - t_first);   // K loop
-    atomicAdd(&g_halo_stamps[2], t_end - t_loop);     // epilogue
-    atomicAdd(&g_halo_stamps[3], 1ull);
-  }
-#endif
-  }  // persistent tile loop
-}
 
 }  // namespace hipac
 #include "halo16.h"
 #include "halo16x2.h"
-#include "band16.h"
 namespace hipac {
 
 // ---------------------------------------------------------------------------------------
@@ -1290,10 +655,7 @@ namespace hipac {
 // applied while the patch is staged (a 3 x 256 table of T values in LDS == the fp32 LUT
 // rounded to T, i.e. exactly what hipac_patches_normalize would have written), so the padded
 // NHWC4 tensor (427 KB per patch written and read back) never exists.
-#ifndef HIPAC_STEM_TILE16
-#define HIPAC_STEM_TILE16 0  // measured: 660 vs 605 ns per patch (+12 % MFMA work outweighs conflict-free reads)
-#endif
-constexpr int kStemTilesPerImage = HIPAC_STEM_TILE16 ? 64 : 56;
+constexpr int kStemTilesPerImage = 56;
 
 template <typename T, bool U8IN>
 __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const void* __restrict__ xin_, const T* __restrict__ wgt,
@@ -1303,18 +665,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const void* __restric
   const T* xin = reinterpret_cast<const T*>(xin_);
   using E = Elem<T>;
   using frag = typename E::frag;
-#if HIPAC_STEM_TILE16
-  // 16 x 16 stem pixels in eight 8 x 4 lane blocks over a 320-byte patch pitch: every ds_read_b128 lane
-  // group of the MFMA loop covers all 16 bank groups (conflict-free); the 7 x 7 pooled tile uses 15 x 15
-  // of them (12 % more MFMA work than the 17 x 15 tile, whose 15-pixel rows cannot avoid 2-way conflicts)
-  constexpr int PTH = 7, PTW = 7;                                       // pooled tile
-  constexpr int STW = 16, STH = 16, NPX = STW * STH;                    // 256 stem pixels
-  constexpr int PROWS = 2 * STH + 5, PCOLS = 40;                        // 37 x 40 input pixels (8 B each)
-#else
   constexpr int PTH = 8, PTW = 7;                                       // pooled tile
   constexpr int STW = 2 * PTW + 1, STH = 2 * PTH + 1, NPX = STW * STH;  // 15 x 17 = 255 stem pixels
   constexpr int PROWS = 2 * STH + 5, PCOLS = 36;                        // 39 x 36 input pixels (8 B each)
-#endif
   static_assert(56 / PTW * (56 / PTH) == kStemTilesPerImage, "tile count");
   constexpr int PPR = PCOLS / 2;                                        // 16-byte pieces per patch row
   constexpr int NPIECE = PROWS * PPR;                                   // 702
@@ -1359,15 +712,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const void* __restric
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     P[i] = (2 * wave + i) * 32 + r;
-#if HIPAC_STEM_TILE16
-    const int sub = 2 * wave + i;                   // block (sub & 1, sub >> 1) of 8 x 4 pixels
-    lx[i] = (sub & 1) * 8 + (r & 7);
-    ly[i] = (sub >> 1) * 4 + (r >> 3);
-#else
     const int Pc = P[i] < NPX ? P[i] : NPX - 1;
     ly[i] = Pc / STW;
     lx[i] = Pc - ly[i] * STW;
-#endif
     // row-major index in the LDS stem tile; lane 255 of the 17 x 15 tile (a pixel that does not exist)
     // keeps its own dummy row 255 -- it must not share a row with pixel 254
     sidx[i] = P[i] < NPX ? ly[i] * STW + lx[i] : P[i];
@@ -1609,9 +956,6 @@ constexpr int kStripSteps = 14;  // 56 pooled rows / 4 per step
 // [64][192] followed by the lo halves [64][192]; hi stays in registers, lo is fetched from LDS per channel plane, and
 // every fragment feeds two MFMAs per (row, row pair).  The pooling stays in fp32 (v_max3 in y, two DPP shifts in x,
 // ReLU) and the pooled rows leave as (hi, lo) pairs [pixel][hi: 64 | lo: 64], hi then lo through the same staging.
-#ifndef HIPAC_NT_STEM
-#define HIPAC_NT_STEM 0  // 1: the strip stem's pooled-map stores are non-temporal (see HIPAC_NT_STORES)
-#endif
 // Q8 (precision fp16q8): the pooled map's q8 tensor [pixel][lo8: 64 | hi8: 64] (halo16x2.h) is written too, from the same staging.
 template <typename T, bool SPLIT = false, bool Q8 = false>
 __global__ __launch_bounds__(512, 2) void stem_pool_strip2_kernel(const unsigned char* __restrict__ x,
@@ -1800,7 +1144,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_strip2_kernel(const unsigned
 #pragma unroll
             for (int m = 0; m < 4; ++m)
               if (m < 3 || lane < 32)
-                store16_out<HIPAC_NT_STEM != 0>(dst0 + g * (2 * 56 * 128) + s_off[m], *reinterpret_cast<const u32x4*>(Sl + (lane + 64 * m) * 16));
+                store16_out(dst0 + g * (2 * 56 * 128) + s_off[m], *reinterpret_cast<const u32x4*>(Sl + (lane + 64 * m) * 16));
             if constexpr (Q8) {
               unsigned char* const qdst0 = out_q + ((((size_t)b * 56 + 4 * ys) * 56 + 28 * side + 14 * st) * 128 + jt * 32) + g * (2 * 56 * 128);
 #pragma unroll
@@ -1897,7 +1241,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_strip2_kernel(const unsigned
 #pragma unroll
           for (int m = 0; m < 4; ++m)
             if (m < 3 || lane < 32)
-              store16_out<HIPAC_NT_STEM != 0>(dst0 + s_off[m], *reinterpret_cast<const u32x4*>(Sl + (lane + 64 * m) * 16));
+              store16_out(dst0 + s_off[m], *reinterpret_cast<const u32x4*>(Sl + (lane + 64 * m) * 16));
           }
         }
         HALO_STAMP(z_te);
@@ -2204,7 +1548,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const T* __restrict
     // cost 18 VGPRs next to 144 of weights): make their inputs opaque per iteration
     asm volatile("" : "+v"(lx), "+v"(ly0));
     const unsigned char* const Hl = smem + buf * U_BYTES + wt * H_BYTES;
-    // the bias is the initial accumulator (register group q = channels wn*32 + 8q + 4h .. +3), as in block_c64.h
+    // the bias is the initial accumulator (register group q = channels wn*32 + 8q + 4h .. +3)
     f32x16 acc[2];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -2498,7 +1842,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_c64_kernel(const T* __restri
 }
 
 }  // namespace hipac
-#include "block_c64.h"
 #include "block16_c64.h"
 namespace hipac {
 
@@ -2618,21 +1961,6 @@ static inline int ensure_dynamic_lds(const void* kern, int lds, bool* done) {
   return 0;
 }
 
-#ifndef HIPAC_HALO_BM256
-#define HIPAC_HALO_BM256 1
-#endif
-#ifndef HIPAC_SPLIT_DBLW
-#define HIPAC_SPLIT_DBLW 1  // fp16x3 layer1: double weight steps (see conv3x3_halo_kernel's DBLW note)
-#endif
-#ifndef HIPAC_HALO_BIG
-#define HIPAC_HALO_BIG 0  // 1: layers 2-4 on one 512-register wave per SIMD (128 x 128 per wave)
-#endif
-#ifndef HIPAC_USE_C64
-#define HIPAC_USE_C64 1
-#endif
-#ifndef HIPAC_USE_HALO
-#define HIPAC_USE_HALO 1
-#endif
 #ifndef HIPAC_BM_A
 #define HIPAC_BM_A 128
 #endif
@@ -2650,82 +1978,21 @@ static inline int ensure_dynamic_lds(const void* kern, int lds, bool* done) {
 #ifndef HIPAC_BN_A
 #define HIPAC_BN_A 128
 #endif
-#ifndef HIPAC_S2_WIDE
-#define HIPAC_S2_WIDE 1  // layers 3-4 entry convs on 256 x 256 tiles of 128 x 64 wave tiles (see launch_conv)
-#endif
-#ifndef HIPAC_S2_BM
-#define HIPAC_S2_BM 256
-#endif
-#ifndef HIPAC_S2_BN
-#define HIPAC_S2_BN 256
-#endif
-#ifndef HIPAC_S2_WTM
-#define HIPAC_S2_WTM 128
-#endif
-#ifndef HIPAC_S2_NSTAGE
-#define HIPAC_S2_NSTAGE 2
-#endif
-#ifndef HIPAC_HALO_MF16
-#define HIPAC_HALO_MF16 1  // layers 2-4 stride-1 convs on v_mfma_f32_16x16x32 (halo16.h); 0: the 32x32x16 form
-#endif
-// the halo kernel of a layer: the 16x16x32 form for the plain 16-bit precisions on 256 x 128 tiles, else the 32x32x16 form
-template <typename T, int CIN, int COUT, int H, int W, int BM, int BN, int NSW, bool RELU, bool RESID, bool OUTF32, bool SPLIT, int PCIN,
-          bool DBLW, bool POOL = false>
-static auto halo_kernel_of() {
-  if constexpr (HIPAC_HALO_MF16 && !SPLIT && sizeof(T) == 2 && BM == 256 && BN == 128)
-    return conv3x3_halo16_kernel<T, CIN, COUT, H, W, BM, BN, NSW, RELU, RESID, OUTF32, PCIN, POOL>;
-  else {
-    static_assert(!POOL, "the pooled epilogue exists in the 16x16x32 halo kernel only");
-    return conv3x3_halo_kernel<T, CIN, COUT, H, W, BM, BN, NSW, RELU, RESID, OUTF32, SPLIT, 2, 2, 2, PCIN, DBLW>;
-  }
-}
-// does the last conv of the network (512 -> 512, 7 x 7) have the pooled epilogue in this build and precision?
-template <typename T, bool SPLIT>
-constexpr bool halo_pool_available() { return HIPAC_HALO_MF16 && HIPAC_H16_DIRECT && HIPAC_USE_HALO && !HIPAC_HALO_BIG && !SPLIT && sizeof(T) == 2; }
 template <int COUT> struct TileCfg { static constexpr int BM = HIPAC_BM_A, BN = (COUT % HIPAC_BN_A == 0 ? HIPAC_BN_A : 128), NSTAGE = HIPAC_NSTAGE_A; };
 template <> struct TileCfg<64> { static constexpr int BM = HIPAC_BM_64, BN = 64, NSTAGE = HIPAC_NSTAGE_B; };
 
-#ifndef HIPAC_S2_HALO16
-#define HIPAC_S2_HALO16 1  // the 3x3 / stride 2 entry convs on halo16's stride-2 form (whole-pixel plane bands); 0: band16.h
-#endif
-#ifndef HIPAC_S2_HALO16_MAXCIN
-#define HIPAC_S2_HALO16_MAXCIN 512  // ... up to this many input channels.  Above it: band16.h's double-buffered half-chunk bands --
-                                    // measured EQUAL for layers 3-4 (114 / 102 vs 116 / 103 ns per patch: what the hidden band round trips
-                                    // gain, the 64-byte rows and the doubled per-tap address work cost), slower for layer2 (165 vs 183)
-#endif
-#ifndef HIPAC_BLK16
-#define HIPAC_BLK16 1  // the fused layer1 block on v_mfma_f32_16x16x32 (block16_c64.h); 0: the 32x32x16 form (block_c64.h)
-#endif
-#ifndef HIPAC_BAND16
-#define HIPAC_BAND16 1  // the 3x3 / stride 2 entry convs of layers 2-4 on the half-chunk band kernel (band16.h); layer2's projection
-                        // shortcut then folds into its block's second conv as layers 3-4's do
-#endif
-#ifndef HIPAC_BAND16_S1
-#define HIPAC_BAND16_S1 0  // ... the stride-1 ones too (measured: 2-3 % SLOWER than halo16 -- the hidden band round trip does not
-                           // pay for twice the per-tap address work and 64-byte weight rows; they stay on the halo16 kernel)
-#endif
-template <typename T, int CIN, int COUT, int HO, int STRIDE, bool RELU, bool RESID, int PCIN>
-static int launch_band16(const void* in, const ConvW& w, const void* resid, void* out, int n, hipStream_t s, const void* wgt_p = nullptr,
-                         const float* bias = nullptr) {
-  constexpr int BM = 256, BN = 128;
-  constexpr int LEAD = HO + 1, TRAIL = STRIDE == 1 ? HO + 1 : 0;
-  constexpr int NPW = (4 + LEAD + BM + TRAIL + 63) / 64;
-  constexpr int LDS = 2 * NPW * 4 * 1024 + HIPAC_B16_NSLOT * 8192;
-  auto kern = conv3x3_band16_kernel<T, CIN, COUT, HO, HO, STRIDE, BM, BN, RELU, RESID, PCIN>;
-  static bool attr_done[kMaxDevices] = {};
-  if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
-  const int M = n * HO * HO;
-  const int n_mtiles = (M + BM - 1) / BM;
-  const int mt8 = (n_mtiles + 7) / 8 * 8;
-  const int n_vtiles = mt8 * (COUT / BN);
-  dim3 grid(n_vtiles < HIPAC_HALO_GRID ? n_vtiles : HIPAC_HALO_GRID);
-  hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const T*)in, (const T*)w.w, bias ? bias : w.bias, (const T*)resid, (T*)out, M, n, n_mtiles,
-                     (const T*)wgt_p);
-  return (int)hipGetLastError();
-}
+// dynamic LDS of the stride-1 halo16 kernel: the band, then the deepest weight ring (NSW slots) that keeps two workgroups per
+// CU, or the kernel's STG_BYTES if that is larger (its S_BYTES)
+template <int W, int BM, int BN>
+struct Halo16Lds {
+  static constexpr int A_BYTES = halo_band_pieces(W, BM) * 1024;
+  static constexpr int STG = 4 * 32 * (BN / 2 * 4 + 16);
+  static constexpr int NSW = (A_BYTES + 3 * BN * 128 <= 80 * 1024) ? 3 : 2;
+  static constexpr int LDS = A_BYTES + (NSW * BN * 128 > STG ? NSW * BN * 128 : STG);
+};
 
 template <typename T, int CIN, int COUT, int HI, int WI, int KS, int STRIDE, bool RELU, bool RESID,
-          bool OUTF32, bool STEM = false, bool SPLIT = false, bool POOL = false>
+          bool OUTF32, bool STEM = false, bool POOL = false>
 static int launch_conv(const void* in, const ConvW& w, const void* resid, void* out, int n, hipStream_t s,
                        const char* zero_page = nullptr) {
   constexpr int PAD = STEM ? 0 : KS / 2;
@@ -2738,34 +2005,13 @@ static int launch_conv(const void* in, const ConvW& w, const void* resid, void* 
     dim3 grid((M + 127) / 128, COUT / BN);
     hipLaunchKernelGGL((conv_igemm_kernel<T, CIN, COUT, HI, WI, KS, STRIDE, BN, RELU, RESID, OUTF32, STEM>),
                        grid, dim3(256), 0, s, (const T*)in, (const T*)w.w, w.bias, (const T*)resid, out, M);
-  } else if constexpr (HIPAC_USE_C64 && !SPLIT && KS == 3 && STRIDE == 1 && CIN == 64 && COUT == 64 && HI == 56 && !OUTF32) {
+  } else if constexpr (KS == 3 && STRIDE == 1 && CIN == 64 && COUT == 64 && HI == 56 && !OUTF32) {
     const int n_tiles = n * 49;
     const int n_units = (n_tiles + 1) / 2;
     const int grid = n_units < 512 ? n_units : 512;  // persistent, 2 workgroups per CU
     hipLaunchKernelGGL((conv3x3_c64_kernel<T, RESID, RELU>), dim3(grid), dim3(256), 0, s, (const T*)in, (const T*)w.w,
                        w.bias, (const T*)resid, (T*)out, n_tiles, zero_page);
-  } else if constexpr (HIPAC_USE_HALO && HIPAC_HALO_BIG && !SPLIT && KS == 3 && STRIDE == 1 && COUT >= 128) {
-    // one 512-register wave per SIMD, each wave a 128 pixel x 128 channel tile
-    constexpr int BN = COUT >= 256 ? 256 : 128;
-    constexpr int WM = COUT >= 256 ? 2 : 4, WN = 4 / WM;
-    constexpr int BM = WM * 128;
-    constexpr int A_BYTES = halo_band_pieces(WI, BM) * 1024;
-    constexpr int STG = 4 * 32 * (BN / WN * 4 + 16);
-    constexpr int NSW = (A_BYTES + (3 * BN * 128 > STG ? 3 * BN * 128 : STG) <= 160 * 1024) ? 3 : 2;
-    constexpr int LDS = A_BYTES + (NSW * BN * 128 > STG ? NSW * BN * 128 : STG);
-    auto kern = conv3x3_halo_kernel<T, CIN, COUT, HI, WI, BM, BN, NSW, RELU, RESID, OUTF32, false, WM, WN, 1>;
-    static bool attr_done[kMaxDevices] = {};
-    if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
-    const int n_mtiles = (M + BM - 1) / BM;
-    const int mt8 = (n_mtiles + 7) / 8 * 8;
-    const int n_vtiles = mt8 * (COUT / BN);
-    dim3 grid(n_vtiles < 256 ? n_vtiles : 256);  // persistent: one workgroup per CU
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)resid, out, M, n,
-                       n_mtiles, zero_page, (const T*)nullptr);
-  } else if constexpr (HIPAC_BAND16_S1 && HIPAC_HALO_MF16 && KS == 3 && STRIDE == 1 && !SPLIT && sizeof(T) == 2 && !OUTF32 && COUT % 128 == 0 && HI == WI) {
-    return launch_band16<T, CIN, COUT, HI, 1, RELU, RESID, 0>(in, w, resid, out, n, s);
-  } else if constexpr (HIPAC_S2_HALO16 && HIPAC_BAND16 && HIPAC_HALO_MF16 && KS == 3 && STRIDE == 2 && !SPLIT && sizeof(T) == 2 && !OUTF32 && !RESID && CIN <= HIPAC_S2_HALO16_MAXCIN &&
-                       COUT % 128 == 0 && HI == WI) {
+  } else if constexpr (KS == 3 && STRIDE == 2 && !OUTF32 && !RESID && COUT % 128 == 0 && HI == WI) {
     // the entry convs of layers 2-4 on halo16's stride-2 form: four parity-plane bands per 64-channel chunk
     constexpr int HO = HI / 2, BM = 256, BN = 128, NSW = 2;
     constexpr int LDS = halo_band_pieces(HO, BM) * 1024 + NSW * BN * 128;
@@ -2781,51 +2027,26 @@ static int launch_conv(const void* in, const ConvW& w, const void* resid, void* 
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)nullptr, out, Mo, n, n_mtiles, zero_page,
                        (const T*)nullptr);
     return (int)hipGetLastError();
-  } else if constexpr (HIPAC_BAND16 && HIPAC_HALO_MF16 && KS == 3 && STRIDE == 2 && !SPLIT && sizeof(T) == 2 && !OUTF32 && !RESID && COUT % 128 == 0 && HI == WI) {
-    return launch_band16<T, CIN, COUT, HI / 2, 2, RELU, false, 0>(in, w, nullptr, out, n, s);
-  } else if constexpr (HIPAC_USE_HALO && KS == 3 && STRIDE == 1) {
-    constexpr int BN = COUT >= 128 ? 128 : 64;
-    // 256-pixel tiles (each wave 128 px x 64 ch: 0.75 LDS reads per MFMA, half the weight DMA per
-    // FLOP) wherever the band still leaves room for two workgroups per CU; else 128
-    constexpr int A256 = halo_band_pieces(WI, 256) * 1024;
-    constexpr int BM = (HIPAC_HALO_BM256 && A256 + 2 * BN * 128 <= 80 * 1024) ? 256 : 128;
-    constexpr int A_BYTES = halo_band_pieces(WI, BM) * 1024;
-    constexpr int STG = 4 * 32 * (BN / 2 * 4 + 16);  // epilogue staging, aliases the ring
-    // fp16x3, narrow tiles: double weight steps where two 2-tile ring slots still leave two workgroups per CU (layer1)
-    constexpr bool DBLW = SPLIT && HIPAC_SPLIT_DBLW && (A_BYTES + 4 * BN * 128 <= 80 * 1024);
-    constexpr int NSW = DBLW ? 2 : ((A_BYTES + 3 * BN * 128 <= 80 * 1024) ? 3 : 2);  // deepest ring that keeps 2 workgroups/CU
-    constexpr int RING = NSW * BN * 128 * (DBLW ? 2 : 1);
-    constexpr int LDS = A_BYTES + (RING > STG ? RING : STG);
-    auto kern = halo_kernel_of<T, CIN, COUT, HI, WI, BM, BN, NSW, RELU, RESID, OUTF32, SPLIT, 0, DBLW, POOL>();
+  } else if constexpr (KS == 3 && STRIDE == 1) {
+    // layers 2-4: 256-pixel x 128-channel tiles (each wave 128 px x 64 ch: 0.75 LDS reads per MFMA, half the weight DMA per FLOP)
+    static_assert(COUT % 128 == 0, "the halo16 kernel takes 128-channel tiles");
+    constexpr int BM = 256, BN = 128;
+    using L = Halo16Lds<WI, BM, BN>;
+    auto kern = conv3x3_halo16_kernel<T, CIN, COUT, HI, WI, BM, BN, L::NSW, RELU, RESID, OUTF32, 0, POOL>;
     static bool attr_done[kMaxDevices] = {};  // the attribute is per device; a benign race at worst repeats the call
-    if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
+    if (int rc_attr = ensure_dynamic_lds((const void*)kern, L::LDS, attr_done)) return rc_attr;
     const int n_mtiles = (M + BM - 1) / BM;
     const int mt8 = (n_mtiles + 7) / 8 * 8;
     const int n_vtiles = mt8 * (COUT / BN);
     dim3 grid(n_vtiles < HIPAC_HALO_GRID ? n_vtiles : HIPAC_HALO_GRID);  // persistent; both are multiples of 8
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)resid, out, M, n,
+    hipLaunchKernelGGL(kern, grid, dim3(256), L::LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)resid, out, M, n,
                        n_mtiles, zero_page, (const T*)nullptr);
-  } else if constexpr (HIPAC_S2_WIDE && KS == 3 && STRIDE == 2 && !SPLIT && COUT % HIPAC_S2_BN == 0 && !RESID && !OUTF32) {
-    // plain 3x3 / stride 2 entry convs of layers 3-4 (their projection is folded into the block's second conv): one
-    // 8-wave workgroup per CU, every wave a 128 pixel x 64 channel tile -- 0.75 LDS fragment reads per MFMA instead of 1
-    // and half the LDS-DMA bytes per FLOP of the 128 x 128 tile
-    constexpr int BM = HIPAC_S2_BM, BN = HIPAC_S2_BN, NSTAGE = HIPAC_S2_NSTAGE, WTM = HIPAC_S2_WTM;
-    constexpr int THREADS = (BM / WTM) * (BN / 64) * 64;
-    constexpr int LDS = NSTAGE * (BM + BN) * 128;
-    auto kern = conv_glds_kernel<T, CIN, COUT, HI, WI, KS, STRIDE, BM, BN, NSTAGE, RELU, RESID, OUTF32, false, SPLIT, WTM>;
-    static bool attr_done[kMaxDevices] = {};
-    if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
-    const int n_mtiles = (M + BM - 1) / BM;
-    const int mt8 = (n_mtiles + 7) / 8 * 8;
-    dim3 grid(mt8 * (COUT / BN));
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)resid, out,
-                       M, n_mtiles, zero_page, (const T*)nullptr, (const float*)nullptr, (void*)nullptr);
   } else {
     using C = TileCfg<COUT>;
     constexpr int BM = C::BM, BN = C::BN, NSTAGE = C::NSTAGE;
     constexpr int THREADS = (BM / 64) * (BN / 64) * 64;
     constexpr int LDS = NSTAGE * (BM + BN) * 128;
-    auto kern = conv_glds_kernel<T, CIN, COUT, HI, WI, KS, STRIDE, BM, BN, NSTAGE, RELU, RESID, OUTF32, false, SPLIT>;
+    auto kern = conv_glds_kernel<T, CIN, COUT, HI, WI, KS, STRIDE, BM, BN, NSTAGE, RELU, RESID, OUTF32>;
     static bool attr_done[kMaxDevices] = {};  // the attribute is per device; a benign race at worst repeats the call
     if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
     const int n_mtiles = (M + BM - 1) / BM;
@@ -2842,24 +2063,17 @@ static int launch_conv(const void* in, const ConvW& w, const void* resid, void* 
 template <typename T, int CO, int HO, int PCIN>
 static int launch_conv_projk(const void* tmp, const ConvW& w2, const ConvW& wp, const float* bias_sum, const void* xblk, void* out,
                              int n, hipStream_t s, const char* zero_page) {
-  if constexpr (HIPAC_BAND16_S1 && HIPAC_HALO_MF16 && sizeof(T) == 2)
-    return launch_band16<T, CO, CO, HO, 1, true, false, PCIN>(tmp, w2, xblk, out, n, s, wp.w, bias_sum);
-  constexpr int BN = 128;
-  constexpr int A256 = halo_band_pieces(HO, 256) * 1024;
-  constexpr int BM = (HIPAC_HALO_BM256 && A256 + 2 * BN * 128 <= 80 * 1024) ? 256 : 128;
-  constexpr int A_BYTES = halo_band_pieces(HO, BM) * 1024;
-  constexpr int NSW = (A_BYTES + 3 * BN * 128 <= 80 * 1024) ? 3 : 2;
-  constexpr int STG = 4 * 32 * (BN / 2 * 4 + 16);
-  constexpr int LDS = A_BYTES + (NSW * BN * 128 > STG ? NSW * BN * 128 : STG);
-  auto kern = halo_kernel_of<T, CO, CO, HO, HO, BM, BN, NSW, true, false, false, false, PCIN, false>();
+  constexpr int BM = 256, BN = 128;
+  using L = Halo16Lds<HO, BM, BN>;
+  auto kern = conv3x3_halo16_kernel<T, CO, CO, HO, HO, BM, BN, L::NSW, true, false, false, PCIN>;
   static bool attr_done[kMaxDevices] = {};
-  if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
+  if (int rc_attr = ensure_dynamic_lds((const void*)kern, L::LDS, attr_done)) return rc_attr;
   const int M = n * HO * HO;
   const int n_mtiles = (M + BM - 1) / BM;
   const int mt8 = (n_mtiles + 7) / 8 * 8;
   const int n_vtiles = mt8 * (CO / BN);
   dim3 grid(n_vtiles < HIPAC_HALO_GRID ? n_vtiles : HIPAC_HALO_GRID);
-  hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, (const T*)tmp, (const T*)w2.w, bias_sum, (const T*)xblk, out, M, n, n_mtiles,
+  hipLaunchKernelGGL(kern, grid, dim3(256), L::LDS, s, (const T*)tmp, (const T*)w2.w, bias_sum, (const T*)xblk, out, M, n, n_mtiles,
                      zero_page, (const T*)wp.w);
   return (int)hipGetLastError();
 }
@@ -2876,7 +2090,7 @@ static int launch_dgrad_s2_class(const void* g, const void* wc, const float* zer
   constexpr int BM = C::BM, BN = C::BN, NSTAGE = C::NSTAGE;
   constexpr int THREADS = (BM / 64) * (BN / 64) * 64;
   constexpr int LDS = NSTAGE * (BM + BN) * 128;
-  auto kern = conv_glds_kernel<T, CG, CX, HC, HC, 1, 1, BM, BN, NSTAGE, false, false, false, false, false, 64, TKH, TKW, 4 | (PY << 1) | PX>;
+  auto kern = conv_glds_kernel<T, CG, CX, HC, HC, 1, 1, BM, BN, NSTAGE, false, false, false, false, TKH, TKW, 4 | (PY << 1) | PX>;
   static bool attr_done[kMaxDevices] = {};
   if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
   const int M = n * HC * HC;
@@ -2921,42 +2135,33 @@ static int launch_dgrad_s2_v1(const void* g, const void* wc, const float* zero_b
   return launch_dgrad_s2_class_v1<T, CG, CX, HC, 2, 2, 1, 1>(g, w + 5 * blk, zero_bias, dx, n, s);
 }
 
-#ifndef HIPAC_USE_S2C64
-#define HIPAC_USE_S2C64 1  // layer2's 3x3/2 conv + projection on the register-weight kernel
-#endif
-#ifndef HIPAC_FUSE_PROJ
-#define HIPAC_FUSE_PROJ 1
-#endif
-#ifndef HIPAC_FUSE_PROJ_MAXCO
-#define HIPAC_FUSE_PROJ_MAXCO 256  // layer4 (512): 181 ns fused at 251 VGPRs vs 118 + 36 separate
-#endif
-
 // 3x3 / stride 2 conv (+BN+ReLU) of a down-sampling BasicBlock with its 1x1 / stride 2 projection
-// shortcut (+BN) riding along (conv_glds_kernel<..., PROJ = true>): x -> (out, out_p)
-template <typename T, int CIN, int COUT, int HI, bool SPLIT = false>
+// shortcut (+BN) riding along: x -> (out, out_p).  Layer2 on the register-weight kernel, layer3 on
+// conv_glds_kernel<..., PROJ = true>
+template <typename T, int CIN, int COUT, int HI>
 static int launch_down(const void* in, const ConvW& w, const ConvW& wp, void* out, void* out_p, int n, hipStream_t s,
                        const char* zero_page) {
-  if constexpr (HIPAC_USE_S2C64 && !SPLIT && CIN == 64 && COUT == 128 && HI == 56) {
+  if constexpr (CIN == 64 && COUT == 128 && HI == 56) {
     const int n_tiles = n * 28;
     const int grid = n_tiles < 512 ? n_tiles : 512;  // persistent, 2 workgroups per CU
     hipLaunchKernelGGL((conv3x3s2_c64_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)in, (const T*)w.w, w.bias,
                        (const T*)wp.w, wp.bias, (T*)out, (T*)out_p, n_tiles, zero_page);
-    return (int)hipGetLastError();
+  } else {
+    using C = TileCfg<COUT>;
+    constexpr int BM = C::BM, BN = C::BN, NSTAGE = C::NSTAGE;
+    constexpr int THREADS = (BM / 64) * (BN / 64) * 64;
+    constexpr int LDS = NSTAGE * (BM + BN) * 128;
+    constexpr int HO = HI / 2;
+    const int M = n * HO * HO;
+    auto kern = conv_glds_kernel<T, CIN, COUT, HI, HI, 3, 2, BM, BN, NSTAGE, true, false, false, true>;
+    static bool attr_done[kMaxDevices] = {};
+    if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
+    const int n_mtiles = (M + BM - 1) / BM;
+    const int mt8 = (n_mtiles + 7) / 8 * 8;
+    dim3 grid(mt8 * (COUT / BN));
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)nullptr, out, M,
+                       n_mtiles, zero_page, (const T*)wp.w, wp.bias, out_p);
   }
-  using C = TileCfg<COUT>;
-  constexpr int BM = C::BM, BN = C::BN, NSTAGE = C::NSTAGE;
-  constexpr int THREADS = (BM / 64) * (BN / 64) * 64;
-  constexpr int LDS = NSTAGE * (BM + BN) * 128;
-  constexpr int HO = HI / 2;
-  const int M = n * HO * HO;
-  auto kern = conv_glds_kernel<T, CIN, COUT, HI, HI, 3, 2, BM, BN, NSTAGE, true, false, false, true, SPLIT>;
-  static bool attr_done[kMaxDevices] = {};
-  if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
-  const int n_mtiles = (M + BM - 1) / BM;
-  const int mt8 = (n_mtiles + 7) / 8 * 8;
-  dim3 grid(mt8 * (COUT / BN));
-  hipLaunchKernelGGL(kern, grid, dim3(THREADS), LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)nullptr, out, M,
-                     n_mtiles, zero_page, (const T*)wp.w, wp.bias, out_p);
   return (int)hipGetLastError();
 }
 
@@ -2975,10 +2180,6 @@ struct Q8Map {
   size_t q8;
   void* of(const void* pairs) const { return ws + q8 + (size_t)((const char*)pairs - ws) / 2; }
 };
-#ifndef HIPAC_X3_HALO16
-#define HIPAC_X3_HALO16 1  // fp16x3: every 3x3 conv on halo16x2.h's X3 form (16x16x32 MFMA, parity-plane entry convs, folded projection, pooled head);
-                           // 0: round 3's SPLIT forms of the 32x32x16 kernels
-#endif
 template <int CIN, int COUT, int HW, bool RELU, bool RESID, bool Q8OUT, bool POOL, bool OUTF32 = false, bool S2 = false, int PCIN = 0, bool LO16 = true,
           bool X3 = false>  // HW: the OUTPUT map
 static int launch_halo16x2(const void* in, const void* in_q, const ConvW& w, const void* resid, void* out, void* out_q, int n, hipStream_t s,
@@ -3021,7 +2222,7 @@ struct OpRange {
 
 // One ResNet stage = two BasicBlocks.  CI/HI: input channels / spatial size,
 // CO/HO: output.  STRIDE 2 stages carry the 1x1/2 projection shortcut.
-template <typename T, int CI, int CO, int HI, int STRIDE, bool LAST, bool SPLIT = false, int PM = 0>
+template <typename T, int CI, int CO, int HI, int STRIDE, bool LAST, int PM = 0>
 static int run_stage(const Net& net, int stage, const void* x, void* tmp, void* ds, void* o0, void* o1, int n,
                      hipStream_t s, OpRange& ops, bool fuse_blocks = false, void* pool_part = nullptr, Q8Map qm = Q8Map{nullptr, 0}) {
   constexpr int HO = HI / STRIDE;
@@ -3032,7 +2233,7 @@ static int run_stage(const Net& net, int stage, const void* x, void* tmp, void* 
     // the pair modes on halo16x2.h -- PM 1: precision fp16q8 (pair + q8 tensors), PM 2: fp16x3 (pairs only, three f16 products).
     // Stride-2 stages: the entry conv on the parity-plane form, the 1x1 / stride 2 projection shortcut folded into the block's second
     // conv as extra K steps (its op slot is empty).  A block's first conv leaves the lo plane out in fp16q8 (nothing reads it).
-    static_assert(SPLIT && sizeof(T) == 2, "the pair layout");
+    static_assert(sizeof(T) == 2, "the pair layout");
     auto Q = [&](const void* pairs) -> void* { return PM == 1 ? qm.of(pairs) : nullptr; };
     if constexpr (STRIDE == 1) {
       if (ops.take()) HIPAC_TRY((launch_pairconv<PM, CI, CO, HO, false, true, false, false, false, 0, false>(x, Q(x), bw[0], nullptr, tmp, Q(tmp), n, s)));
@@ -3054,22 +2255,22 @@ static int run_stage(const Net& net, int stage, const void* x, void* tmp, void* 
       }
     }
     return 0;
-  } else {  // (the single-value precisions, and HIPAC_X3_HALO16=0: round 3's SPLIT kernels)
+  } else {  // the single-value precisions
   // second conv of the stage's second block; for the network's last one (LAST) either the fp32 map or, with `pool_part`,
-  // the per-image partial sums of the global average pool (halo16.h, POOL)
+  // the per-image partial sums of the global average pool (halo16.h, POOL; the 16-bit precisions)
   auto launch_last = [&](const void* in_, const void* resid_, void* out_) -> int {
-    if constexpr (LAST && halo_pool_available<T, SPLIT>()) {
+    if constexpr (LAST && sizeof(T) == 2) {
       if (pool_part)
-        return launch_conv<T, CO, CO, HO, HO, 3, 1, true, true, true, false, SPLIT, true>(in_, bw1[1], resid_, pool_part, n, s, z);
+        return launch_conv<T, CO, CO, HO, HO, 3, 1, true, true, true, false, true>(in_, bw1[1], resid_, pool_part, n, s, z);
     }
-    return launch_conv<T, CO, CO, HO, HO, 3, 1, true, true, LAST, false, SPLIT>(in_, bw1[1], resid_, out_, n, s, z);
+    return launch_conv<T, CO, CO, HO, HO, 3, 1, true, true, LAST>(in_, bw1[1], resid_, out_, n, s, z);
   };
-  if constexpr (CI == 64 && CO == 64 && HI == 56 && STRIDE == 1 && sizeof(T) == 2 && !SPLIT) {
+  if constexpr (CI == 64 && CO == 64 && HI == 56 && STRIDE == 1 && sizeof(T) == 2) {
     if (fuse_blocks) {
       // layer1: each BasicBlock is one launch (conv1 -> conv2 + shortcut on chip); the conv2 op slots stay empty
       const int per_xcd = 4 * ((n + 7) / 8);                   // strips on the busiest XCD
       const int grid = 8 * (per_xcd < 32 ? per_xcd : 32);      // persistent: one 8-wave workgroup per CU
-      auto blk_kern = HIPAC_BLK16 ? block16_c64_kernel<T> : block_c64_kernel<T>;
+      auto blk_kern = block16_c64_kernel<T>;
       if (ops.take()) {
         hipLaunchKernelGGL(blk_kern, dim3(grid), dim3(512), 0, s, (const T*)x, (const T*)bw[0].w,
                            bw[0].bias, (const T*)bw[1].w, bw[1].bias, (T*)o0, n);
@@ -3087,51 +2288,51 @@ static int run_stage(const Net& net, int stage, const void* x, void* tmp, void* 
   }
   // block 0
   const void* idt = x;
-  if constexpr (STRIDE == 2 && sizeof(T) == 2 && !SPLIT && (CO >= 256 || (HIPAC_BAND16 && HIPAC_HALO_MF16))) {
+  if constexpr (STRIDE == 2 && sizeof(T) == 2) {
     if (net.projk && net.bias_c2p[stage - 1]) {
-      // layers 3, 4: plain 3x3/2 entry conv; the projection rides in the SECOND conv as extra K steps (its op slot is empty)
+      // layers 2-4: plain 3x3/2 entry conv; the projection rides in the SECOND conv as extra K steps (its op slot is empty)
       if (ops.take())
-        HIPAC_TRY((launch_conv<T, CI, CO, HI, HI, 3, STRIDE, true, false, false, false, false>(x, bw[0], nullptr, tmp, n, s, z)));
+        HIPAC_TRY((launch_conv<T, CI, CO, HI, HI, 3, STRIDE, true, false, false>(x, bw[0], nullptr, tmp, n, s, z)));
       (void)ops.take();
       if (ops.take())
         HIPAC_TRY((launch_conv_projk<T, CO, HO, CI>(tmp, bw[1], net.down[stage - 1], net.bias_c2p[stage - 1], x, o0, n, s, z)));
-      if (ops.take()) HIPAC_TRY((launch_conv<T, CO, CO, HO, HO, 3, 1, true, false, false, false, SPLIT>(o0, bw1[0], nullptr, tmp, n, s, z)));
+      if (ops.take()) HIPAC_TRY((launch_conv<T, CO, CO, HO, HO, 3, 1, true, false, false>(o0, bw1[0], nullptr, tmp, n, s, z)));
       if (ops.take()) HIPAC_TRY((launch_last(tmp, o0, o1)));
       return 0;
     }
   }
-  if constexpr (STRIDE == 2 && sizeof(T) == 2 && HIPAC_FUSE_PROJ && CO <= HIPAC_FUSE_PROJ_MAXCO) {
+  if constexpr (STRIDE == 2 && sizeof(T) == 2 && CO <= 256) {
     // one launch: conv1 and the projection shortcut (the op slot of the projection stays empty).
     // Not for layer4: its second accumulator set pushes the kernel past 256 registers, i.e. to
     // one workgroup per CU (measured 349 ns/img fused vs 132 + 37 separate).
-    if (ops.take()) HIPAC_TRY((launch_down<T, CI, CO, HI, SPLIT>(x, bw[0], net.down[stage - 1], tmp, ds, n, s, z)));
+    if (ops.take()) HIPAC_TRY((launch_down<T, CI, CO, HI>(x, bw[0], net.down[stage - 1], tmp, ds, n, s, z)));
     (void)ops.take();
     idt = ds;
   } else {
     if (ops.take())
-      HIPAC_TRY((launch_conv<T, CI, CO, HI, HI, 3, STRIDE, true, false, false, false, SPLIT>(x, bw[0], nullptr, tmp, n, s, z)));
+      HIPAC_TRY((launch_conv<T, CI, CO, HI, HI, 3, STRIDE, true, false, false>(x, bw[0], nullptr, tmp, n, s, z)));
     if constexpr (STRIDE != 1 || CI != CO) {
       if (ops.take())
-        HIPAC_TRY((launch_conv<T, CI, CO, HI, HI, 1, STRIDE, false, false, false, false, SPLIT>(x, net.down[stage - 1], nullptr, ds, n, s, z)));
+        HIPAC_TRY((launch_conv<T, CI, CO, HI, HI, 1, STRIDE, false, false, false>(x, net.down[stage - 1], nullptr, ds, n, s, z)));
       idt = ds;
     }
   }
-  if (ops.take()) HIPAC_TRY((launch_conv<T, CO, CO, HO, HO, 3, 1, true, true, false, false, SPLIT>(tmp, bw[1], idt, o0, n, s, z)));
+  if (ops.take()) HIPAC_TRY((launch_conv<T, CO, CO, HO, HO, 3, 1, true, true, false>(tmp, bw[1], idt, o0, n, s, z)));
   // block 1
-  if (ops.take()) HIPAC_TRY((launch_conv<T, CO, CO, HO, HO, 3, 1, true, false, false, false, SPLIT>(o0, bw1[0], nullptr, tmp, n, s, z)));
+  if (ops.take()) HIPAC_TRY((launch_conv<T, CO, CO, HO, HO, 3, 1, true, false, false>(o0, bw1[0], nullptr, tmp, n, s, z)));
   if (ops.take()) HIPAC_TRY((launch_last(tmp, o0, o1)));
   return 0;
   }
 }
 
-template <typename T, bool SPLIT = false, int PM = 0>  // PM: pair mode (run_stage)
+template <typename T, int PM = 0>  // PM: pair mode (run_stage)
 static int run_trunk(const Net& net, const Plan& p, char* ws, const void* xin, int n_early, int img_off, int n_late,
                      hipStream_t s, int first, int last) {
   OpRange ops{first, last, 0};
   const Q8Map qm{ws, p.q8};
   const int ne = n_early, nl = n_late;
   bool fused_done = false;
-  if constexpr (SPLIT) {
+  if constexpr (PM != 0) {
     if (p.u8_input && p.stem_strip) {
       // fp16x3, uint8 input: the strip kernel with split weights (bytes are exact in fp16); op 1 = nothing
       if (ops.take()) {
@@ -3183,7 +2384,7 @@ static int run_trunk(const Net& net, const Plan& p, char* ws, const void* xin, i
       fused_done = true;
     }
   }
-  if constexpr (!SPLIT)
+  if constexpr (PM == 0)
   if (!fused_done) {
   if (ops.take())
     HIPAC_TRY((launch_conv<T, 4, 64, 224, 224, 7, 2, true, false, false, true>(xin, net.stem, nullptr, ws + p.stem, ne, s)));
@@ -3196,14 +2397,14 @@ static int run_trunk(const Net& net, const Plan& p, char* ws, const void* xin, i
     }
   // layer2's second block writes straight into this sub-batch's slice of the group buffer
   char* l2out = ws + p.blk[3] + (size_t)img_off * 28 * 28 * 128 * p.esz;
-  HIPAC_TRY((run_stage<T, 64, 64, 56, 1, false, SPLIT, PM>(net, 0, ws + p.pool, ws + p.tmp_e, nullptr, ws + p.blk[0], ws + p.blk[1], ne, s, ops,
+  HIPAC_TRY((run_stage<T, 64, 64, 56, 1, false, PM>(net, 0, ws + p.pool, ws + p.tmp_e, nullptr, ws + p.blk[0], ws + p.blk[1], ne, s, ops,
                                                            p.l1_fused != 0, nullptr, qm)));
-  HIPAC_TRY((run_stage<T, 64, 128, 56, 2, false, SPLIT, PM>(net, 1, ws + p.blk[1], ws + p.tmp_e, ws + p.ds_e, ws + p.blk[2], l2out, ne, s, ops, false,
+  HIPAC_TRY((run_stage<T, 64, 128, 56, 2, false, PM>(net, 1, ws + p.blk[1], ws + p.tmp_e, ws + p.ds_e, ws + p.blk[2], l2out, ne, s, ops, false,
                                                             nullptr, qm)));
-  HIPAC_TRY((run_stage<T, 128, 256, 28, 2, false, SPLIT, PM>(net, 2, ws + p.blk[3], ws + p.tmp_l, ws + p.ds_l, ws + p.blk[4], ws + p.blk[5], nl, s, ops,
+  HIPAC_TRY((run_stage<T, 128, 256, 28, 2, false, PM>(net, 2, ws + p.blk[3], ws + p.tmp_l, ws + p.ds_l, ws + p.blk[4], ws + p.blk[5], nl, s, ops,
                                                              false, nullptr, qm)));
-  HIPAC_TRY((run_stage<T, 256, 512, 14, 2, true, SPLIT, PM>(net, 3, ws + p.blk[5], ws + p.tmp_l, ws + p.ds_l, ws + p.blk[6], ws + p.blk[7], nl, s, ops,
-                                                            false, p.pool_head && (PM != 0 || halo_pool_available<T, SPLIT>()) ? ws + p.part : nullptr, qm)));
+  HIPAC_TRY((run_stage<T, 256, 512, 14, 2, true, PM>(net, 3, ws + p.blk[5], ws + p.tmp_l, ws + p.ds_l, ws + p.blk[6], ws + p.blk[7], nl, s, ops,
+                                                            false, p.pool_head && sizeof(T) == 2 ? ws + p.part : nullptr, qm)));
   return 0;
 }
 

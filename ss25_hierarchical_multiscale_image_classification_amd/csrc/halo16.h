@@ -28,7 +28,7 @@
 //
 // Everything else (contiguous band per 64-channel chunk by LDS-DMA, zero slots by parity for image-edge taps, 2-slot weight
 // ring one tap ahead through a buffer descriptor, persistent workgroups, per-wave staged epilogue, folded projection
-// PCIN) is the 32x32 kernel's design; see the comment above conv3x3_halo_kernel.
+// PCIN) is described above halo_band_pieces in conv_igemm.h.
 #pragma once
 
 namespace hipac {
@@ -45,7 +45,7 @@ template <> struct Elem16<_Float16> {
   }
 };
 
-// The K step's instruction stream is written out (HIPAC_H16_ASM): hipcc orders every ds_read_b128 right in front of an
+// The K step's instruction stream is written out: hipcc orders every ds_read_b128 right in front of an
 // `s_waitcnt lgkmcnt(0)` (it does not count LDS reads in flight in this loop), which with 16-cycle MFMAs in groups of four
 // leaves ~64 cycles of cover for an LDS round trip, and it renames accumulators between MFMAs (extra live ranges, s_nop
 // padding).  Here: reads HIPAC_H16_AHEAD sub-tiles ahead, counted waits, accumulators updated in place.  asm volatile
@@ -82,7 +82,7 @@ __device__ __forceinline__ void wait_lgkmcnt() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
 }
 
-// tap order inside a half-chunk.  Stride 1: row-major.  Stride 2: by plane -- (1,1): taps (0,0) (0,2) (2,0) (2,2); (0,1): (1,0)
+// tap order inside a 64-channel chunk.  Stride 1: row-major.  Stride 2: by plane -- (1,1): taps (0,0) (0,2) (2,0) (2,2); (0,1): (1,0)
 // (1,2); (1,0): (0,1) (2,1); (0,0): (1,1) -- so that a plane's taps are consecutive and the band changes at positions 0, 4, 6, 8.
 // (Arithmetic on a packed constant, not a table: a table indexed at run time becomes a scalar LOAD, and scalar loads share the
 // lgkmcnt counter the written-out MFMA stream counts its LDS reads with.)
@@ -92,35 +92,17 @@ template <int STRIDE> __host__ __device__ constexpr int b16_kw(int k) { return b
 __host__ __device__ constexpr int perm16(int n) { return n < 4 ? 2 * n : (n < 12 ? 2 * n - 7 : 2 * n - 16); }
 __host__ __device__ constexpr int perm16_inv(int j) { return (j & 1) ? (j + 7) / 2 : (j < 8 ? j / 2 : j / 2 + 8); }
 
-#ifndef HIPAC_H16_ASM
-#define HIPAC_H16_ASM 1   // 1: the K step as written-out asm statements (see Asm16); 0: builtins, hipcc's schedule
-#endif
-#ifndef HIPAC_H16_DIRECT
-#define HIPAC_H16_DIRECT 1  // 1: epilogue straight from the accumulators (v_permlane16_swap pairs 16-lane rows into 16-byte
-                            // items), the next tile's band AND first weight tiles prefetched behind it; 0: staged through LDS
-#endif
-#ifndef HIPAC_H16_RESID_MFMA
-#define HIPAC_H16_RESID_MFMA 1  // 1: the residual is added by the matrix pipe (identity "weights" over the residual tile brought
-                                // into LDS by DMA, after the last tap); 0: loaded into registers and added in the epilogue
-#endif
 #ifndef HIPAC_H16_EPI_PRIO
 #define HIPAC_H16_EPI_PRIO 0  // s_setprio level of the epilogue's store loop (the K loop runs at 1)
 #endif
 #ifndef HIPAC_H16_STAGE16
 #define HIPAC_H16_STAGE16 0  // 1: 16-bit outputs leave through a 4 KB LDS transpose per wave as whole cache lines (see STAGE16; measured equal)
 #endif
-#ifndef HIPAC_H16_XCD_CHUNKS
-#define HIPAC_H16_XCD_CHUNKS 1  // 1: M-tiles dealt to the XCDs in contiguous runs (neighbouring tiles share W + 1 band pixels: L2 hits;
-                                // entry convs -2..-3 %, the rest +-0), 0: round-robin
-#endif
 #ifndef HIPAC_H16_ABL
 #define HIPAC_H16_ABL 0  // developer builds (wrong results): 1 no per-step barrier, 2 no weight DMA in the K loop, 4 no fragment waits, 8 no wait for the weight DMA, 16 no image-edge selects, 32 no stores, 64 (stride-2 form) no band reload at the plane switches, 128 stores wrapped into a 16 K-pixel window (the instructions without the HBM write traffic)
 #endif
-#ifndef HIPAC_H16_SB
-#define HIPAC_H16_SB 1
-#endif
 #ifndef HIPAC_H16_AHEAD
-#define HIPAC_H16_AHEAD (HIPAC_H16_ASM ? 3 : 2)  // activation fragments in flight ahead of the sub-tile whose MFMAs are being issued
+#define HIPAC_H16_AHEAD 3  // activation fragments in flight ahead of the sub-tile whose MFMAs are being issued
 #endif
 
 // POOL (the network's last conv: OUTF32, RELU): instead of storing the fp32 map [n][H*W][COUT] (0.1 MB per patch, read back by
@@ -163,7 +145,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
   constexpr int WM = 2, WN = 2;                     // 4 waves: pixel parts x channel parts
   constexpr int WPX = BM / WM;                      // pixels per wave
   constexpr int MT = WPX / 16;                      // 16-pixel sub-tiles per wave (8)
-  constexpr int G32 = WPX / 32;                     // 32-pixel epilogue groups per wave
   constexpr int WTN = BN / WN, NT = WTN / 16;       // channels per wave, 16-wide tiles per wave (4)
   constexpr int A_PIECES = halo_band_pieces(W, BM);
   constexpr int A_BYTES = A_PIECES * 1024;
@@ -172,25 +153,25 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
   constexpr int NTILES_N = COUT / BN;
   constexpr int PCC = PCIN / 64;                    // projection K steps (0: no folded projection)
   constexpr int NSTEP = 9 * CC + PCC;
-  constexpr bool RESID_MFMA = RESID && HIPAC_H16_RESID_MFMA && HIPAC_H16_ASM && HIPAC_H16_DIRECT;  // see "the residual, added on the matrix pipe"
-  constexpr bool EPI_RESID = RESID && !RESID_MFMA;  // the epilogue loads and adds the residual itself
   static_assert(sizeof(T) == 2, "16-bit operands");
   // S2: a 3x3 / STRIDE 2 conv (H x W = the OUTPUT map, the input is 2H x 2W): the nine taps fall on the four parity planes of the
-  // input (band16.h has the geometry), each a stride-1 problem on the output grid, so a K step is unchanged and only the
-  // band differs -- per 64-channel chunk FOUR bands (planes (1,1), (0,1), (1,0), (0,0) with 4 / 2 / 2 / 1 taps), gathered
-  // pixel by pixel (full 128-byte rows), one after the other into the single band buffer.  Each band's DMA round trip is
-  // exposed, which is why layers 3-4 use band16.h's double-buffered half-chunk bands instead; for CIN = 64 (layer2's entry)
-  // a half-chunk band is a HALF cache line per pixel and the DMA engine, not the exposure, bounds that kernel.
-  static_assert(!S2 || (PCIN == 0 && !RESID && !POOL && !OUTF32 && HIPAC_H16_DIRECT && HIPAC_H16_ASM), "stride-2 form: plain entry conv");
-  static_assert(!POOL || (OUTF32 && RELU && HIPAC_H16_DIRECT && (BM + H * W - 1) / (H * W) + 1 <= kPoolSlots && H * W > 16),
+  // input, each a stride-1 problem on the output grid: output (oy, ox) reads input (2 oy + kh - 1, 2 ox + kw - 1), i.e. pixel
+  // (oy + dy, ox + dx) of the parity plane (py, px) = (kh != 1, kw != 1) with dy = -(kh == 0), dx = -(kw == 0).  So a K step is
+  // unchanged and only the band differs -- per 64-channel chunk FOUR bands (planes (1,1), (0,1), (1,0), (0,0) with 4 / 2 / 2 / 1
+  // taps), gathered pixel by pixel (full 128-byte rows), one after the other into the single band buffer.  Each band's DMA round
+  // trip is exposed; double-buffered half-chunk bands (64-byte rows) measured equal for layers 3-4 and slower for layer2.
+  static_assert(!S2 || (PCIN == 0 && !RESID && !POOL && !OUTF32), "stride-2 form: plain entry conv");
+  static_assert(!POOL || (OUTF32 && RELU && (BM + H * W - 1) / (H * W) + 1 <= kPoolSlots && H * W > 16),
                 "pooled epilogue: the fp32 form of the direct epilogue, maps of more than 16 pixels");
   static_assert(PCIN % 64 == 0 && (PCIN == 0 || !RESID), "folded projection replaces the residual input");
   static_assert((BM == 128 || BM == 256) && WTN % 16 == 0 && COUT % BN == 0 && CIN % 64 == 0 && MT <= 8, "tile shape");
   static_assert((BN / 8) % 4 == 0, "W piece split");
   static_assert(NSW == 2 || NSW == 3, "weight ring depth");
-  constexpr int SROWW = WTN * 4 + 16;               // staging row: WTN fp32 + pad
-  constexpr int STG_BYTES = 4 * 32 * SROWW;         // 4 waves x [32 px][WTN fp32 + pad] epilogue staging
-  constexpr int S_BYTES = NSW * W_BYTES > STG_BYTES ? NSW * W_BYTES : STG_BYTES;  // ring, aliased by the staging
+  // LDS behind the band: the weight ring, or 4 waves x [32 px][WTN fp32 + pad] if that is larger (the size the launchers
+  // reserve, kept from a staged epilogue)
+  constexpr int SROWW = WTN * 4 + 16;
+  constexpr int STG_BYTES = 4 * 32 * SROWW;
+  constexpr int S_BYTES = NSW * W_BYTES > STG_BYTES ? NSW * W_BYTES : STG_BYTES;
   static_assert(A_BYTES + S_BYTES <= 80 * 1024, "LDS: two workgroups per CU");
   // the last sub-tile's taps may read past the tile's own band (tail tiles are not clamped): still inside the band region
   static_assert(BM + 2 * W + 4 <= A_PIECES * 8, "band slots");
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
       }
     }
   };
-  // band of the plane of tap position k (band16.h's order: positions 0-3 plane (1,1), 4-5 (0,1), 6-7 (1,0), 8 (0,0)), chunk cc
+  // band of the plane of tap position k (b16_tap's order: positions 0-3 plane (1,1), 4-5 (0,1), 6-7 (1,0), 8 (0,0)), chunk cc
   auto issue_plane_band = [&](int k, int cc) {
     if constexpr (S2) {
       const int py = k < 4 ? 1 : (k < 6 ? 0 : (k < 8 ? 1 : 0)), px = k < 6 ? 1 : 0;
@@ -258,28 +239,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
     }
   };
 
-  // DIRECT: the next tile's band and first weights are requested BEFORE the epilogue's stores, and vector-memory operations
+  // The next tile's band and first weights are requested BEFORE the epilogue's stores, and vector-memory operations
   // retire in order: at the next tile's first step it is enough to wait until only those stores are outstanding -- if every
   // one of them was issued, i.e. the tile was full (a store whose lanes are all past M may be branched around)
   constexpr int N_EPI_STORES = MT * (OUTF32 ? NT : NT / 2);
   bool prev_full = false;
   for (int vb = blockIdx.x, first_tile = 1;; vb += gridDim.x, first_tile = 0) {
   const int xcd = vb & 7, slot = vb >> 3;
-#if HIPAC_H16_XCD_CHUNKS
   // every XCD takes a contiguous run of M-tiles: neighbouring tiles share W + 1 band pixels, which then hit that XCD's L2
   const int mt_q = (n_mtiles + 7) >> 3;
   const int mt = (slot / NTILES_N) < mt_q ? xcd * mt_q + slot / NTILES_N : n_mtiles;
-#else
-  const int mt = (slot / NTILES_N) * 8 + xcd;
-#endif
   const int nt = slot % NTILES_N;
   if (mt >= n_mtiles) break;  // mt grows with vb on a fixed XCD: nothing valid follows
   const int m0 = mt * BM, n0 = nt * BN;
   const int mlast = (m0 + BM <= M ? m0 + BM : M) - 1;
   const int mstart = m0 - W - 1;
-  constexpr bool DIRECT = HIPAC_H16_DIRECT != 0;
   HALO_STAMP(t_start);
-  if (!DIRECT && !first_tile) __builtin_amdgcn_s_barrier();  // the previous tile's staging reads are done: ring is free
   // weight DMA: LDS row `row` of the tile takes output channel (row & ~15) | perm16_inv(row & 15)
   int w_off[WPW];
   int wp_off[PCC > 0 ? WPW : 1];
@@ -364,7 +339,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
 
   // One K step = 64 channels of one tap = two k32 sub-steps of MT x NT MFMAs.  a_addr[i] = byte address of the lane's
   // fragment of sub-tile i for k32 sub-step 0 (sub-step 1: ^ 64).  `mid` runs once, inside the MFMA stream.
-#if HIPAC_H16_ASM
   const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)ring;  // LDS byte address of the band region
   auto k_step = [&](const unsigned char* wst, const int (&a_addr)[MT], auto&& mid) {
     constexpr int AH = HIPAC_H16_AHEAD;
@@ -400,56 +374,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
     });
     __builtin_amdgcn_s_setprio(0);
   };
-#else
-  auto k_step = [&](const unsigned char* wst, const int (&a_addr)[MT], auto&& mid) {
-    frag wf[2][NT];
-    frag af[HIPAC_H16_AHEAD + 1];
-    constexpr int NS = 2 * MT;  // (k32 sub-step, pixel sub-tile) pairs in issue order
-    auto a_of = [&](int s) -> frag {
-      const int kk = s / MT, i = s % MT;
-      return *reinterpret_cast<const frag*>(Abuf + (kk ? a_addr[i] ^ 64 : a_addr[i]));
-    };
-#pragma unroll
-    for (int j = 0; j < NT; ++j) wf[0][j] = *reinterpret_cast<const frag*>(wst + j * 2048 + rdw0);
-#pragma unroll
-    for (int s = 0; s < HIPAC_H16_AHEAD; ++s) af[s] = a_of(s);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const int kk = s / MT, i = s % MT;
-      if (s + HIPAC_H16_AHEAD < NS) af[(s + HIPAC_H16_AHEAD) % (HIPAC_H16_AHEAD + 1)] = a_of(s + HIPAC_H16_AHEAD);
-      if (kk == 0 && i >= 2 && i < 2 + NT)  // the second sub-step's weight fragments, one per sub-tile
-        wf[1][i - 2] = *reinterpret_cast<const frag*>(wst + (i - 2) * 2048 + (rdw0 ^ 64));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) acc[i][j] = Elem16<T>::mfma(wf[kk][j], af[s % (HIPAC_H16_AHEAD + 1)], acc[i][j]);
-      if (s == MT / 2) mid();
-#if HIPAC_H16_SB
-      __builtin_amdgcn_sched_barrier(0);  // keep the reads HIPAC_H16_AHEAD sub-tiles ahead of their MFMAs, as written
-#endif
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-#endif
-
-  // Epilogue geometry (per WAVE, no workgroup barriers): 32-pixel groups through the wave's private fp32 staging
-  // [32 px][WTN] and out as 16-byte items (8 channels): item = lane + 64k -> pixel item / CPW, channel group lane % CPW.
-  constexpr int CPW = WTN / 8;                      // 8-channel items per pixel (wave's channel half)
-  constexpr int IPT = 32 * CPW / 64;                // items per lane and group
-  static_assert(64 % CPW == 0 && (32 * CPW) % 64 == 0, "epilogue items");
-  const int e_c0 = n0 + wn * WTN + (lane % CPW) * 8;  // first of this lane's 8 output channels
-  const int e_px = lane / CPW;                        // pixel of item k: e_px + k * (64 / CPW)
-  frag rv[2][RESID ? IPT : 1];
-  auto load_resid = [&](auto SUB) {
-    constexpr int i = decltype(SUB)::value;
-    if constexpr (RESID) {
-#pragma unroll
-      for (int k = 0; k < IPT; ++k) {
-        int m = m0 + wm * WPX + i * 32 + e_px + k * (64 / CPW);
-        m = m < M ? m : M - 1;  // unconditional load from a valid row (tail rows are never stored)
-        rv[i & 1][k] = *reinterpret_cast<const frag*>(resid + (size_t)m * COUT + e_c0);
-      }
-    }
-  };
 
 #ifdef HIPAC_HALO_STAMPS
   unsigned long long t_first = 0;
@@ -460,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
     if constexpr (S2) issue_plane_band(0, 0);
     else issue_band_of(m0, 0);
   }
-  if (!DIRECT || first_tile) {  // (DIRECT: the previous tile's epilogue has requested them)
+  if (first_tile) {  // (after the first tile, the previous tile's epilogue has requested them)
 #pragma unroll
     for (int pstep = 0; pstep < NSW - 1; ++pstep)
       if (pstep < NSTEP) issue_w(pstep, pstep);
@@ -479,7 +403,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
       }
       // W(s) must have landed; the band too at tap 0 (it was issued AFTER W(s+1..), so drain everything)
       if (NSW == 3 && tap != 0 && s + 1 < NSTEP) wait_vmcnt<WPW>();
-      else if (DIRECT && s == 0 && prev_full) wait_vmcnt<N_EPI_STORES>();  // the prefetch is older than the epilogue's stores
+      else if (s == 0 && prev_full) wait_vmcnt<N_EPI_STORES>();  // the prefetch is older than the epilogue's stores
       else if (!(HIPAC_H16_ABL & 8) || tap == 0) wait_vmcnt<0>();  // (ablation 8: weight tiles are not waited for)
       if (!(HIPAC_H16_ABL & 1) || tap == 0) __builtin_amdgcn_s_barrier();
 #ifdef HIPAC_HALO_STAMPS
@@ -532,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
     }
   }
 
-  if constexpr (RESID_MFMA) {
+  if constexpr (RESID) {
     // ---- the residual, added on the matrix pipe.  A direct epilogue would have to LOAD it in the accumulator layout: 16 bytes
     // per lane with neighbouring lanes on different pixels -- four times the address-coalescer cycles of a contiguous read,
     // in bursts of 16 loads per wave that queue in front of the other workgroup's weight DMA (measured: 6-8 k cycles to issue
@@ -583,311 +507,184 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
   }
   // ---- epilogue -------------------------------------------------------------------------------
   HALO_STAMP(t_loop);
-#if HIPAC_H16_ASM
   // the accumulators were last written by MFMAs hipcc does not know about: the wait states it would have put in front of
   // their first reader (XDL write -> VALU / LDS read) are spelled out, once per tile
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
-#endif
-  if constexpr (DIRECT) {
-    // ---- direct epilogue: no LDS.  Lane (n, g) holds channels 16 j + 4 g .. + 3 of pixel perm16(n) of every sub-tile: two
-    // packed dwords per 16-wide tile j.  v_permlane16_swap on the dwords of tiles (2 jp, 2 jp + 1) leaves every lane with
-    // 16 contiguous bytes -- row g of the wave stores channels 32 jp + 16 (g & 1) + 8 (g >> 1) .. + 7 -- so one store
-    // instruction writes 64 contiguous bytes per pixel (the 32x32 form of this idea gave 32-byte runs and lost to the
-    // staged form).  The residual arrives in the stored layout and is un-paired by the same swap (an involution).
-    float4 bv[NT];
+  // ---- direct epilogue: no LDS.  Lane (n, g) holds channels 16 j + 4 g .. + 3 of pixel perm16(n) of every sub-tile: two
+  // packed dwords per 16-wide tile j.  v_permlane16_swap on the dwords of tiles (2 jp, 2 jp + 1) leaves every lane with
+  // 16 contiguous bytes -- row g of the wave stores channels 32 jp + 16 (g & 1) + 8 (g >> 1) .. + 7 -- so one store
+  // instruction writes 64 contiguous bytes per pixel (the 32x32 form of this idea gave 32-byte runs and lost to the
+  // staged form).
+  float4 bv[NT];
 #pragma unroll
-    for (int j = 0; j < NT; ++j) bv[j] = *reinterpret_cast<const float4*>(bias + n0 + wn * WTN + 16 * j + 4 * g);
-    const int c_lane = n0 + wn * WTN + 16 * (g & 1) + 8 * (g >> 1);  // + 32 jp: first of the 8 channels this lane stores
-    // STAGE16: the 16-byte items (one pixel each, neighbouring lanes on DIFFERENT pixels: every store instruction touches 16
-    // half lines and costs the address coalescer 4x the cycles of a contiguous one -- removing the stores altogether made the
-    // layer2 / layer3 convs 16-22 % faster, most of it the OTHER workgroup's weight DMA queueing behind these bursts) go through
-    // LDS once more, 32 pixels at a time, and leave as whole 128-byte lines
-    constexpr bool STAGE16 = HIPAC_H16_STAGE16 && !OUTF32 && NSW == 2 && WTN == 64;
-    unsigned char* const Sw16 = Wbuf + W_BYTES + wave * 4096;
-    // ALL of the tile's residual loads are requested up front (the K loop's fragment registers are free now): vector-memory
-    // operations retire in order, so a load requested later would queue behind the next tile's band and weight DMA below
-    u32x4 rq[MT][EPI_RESID && !OUTF32 ? NT / 2 : 1];
-    u32x2 rq32[MT][EPI_RESID && OUTF32 ? NT : 1];
-    auto load_resid_d = [&](auto SUB) {
-      constexpr int i = decltype(SUB)::value;
-      if constexpr (EPI_RESID) {
-        int m = mw0 + 16 * i;
-        m = m < M ? m : M - 1;  // unconditional load from a valid row (tail rows are never stored)
-        if constexpr (OUTF32) {
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            rq32[i][j] = *reinterpret_cast<const u32x2*>(resid + (size_t)m * COUT + n0 + wn * WTN + 16 * j + 4 * g);
-        } else {
-#pragma unroll
-          for (int jp = 0; jp < NT / 2; ++jp)
-            rq[i][jp] = *reinterpret_cast<const u32x4*>(resid + (size_t)m * COUT + c_lane + 32 * jp);
-        }
+  for (int j = 0; j < NT; ++j) bv[j] = *reinterpret_cast<const float4*>(bias + n0 + wn * WTN + 16 * j + 4 * g);
+  const int c_lane = n0 + wn * WTN + 16 * (g & 1) + 8 * (g >> 1);  // + 32 jp: first of the 8 channels this lane stores
+  // STAGE16: the 16-byte items (one pixel each, neighbouring lanes on DIFFERENT pixels: every store instruction touches 16
+  // half lines and costs the address coalescer 4x the cycles of a contiguous one -- removing the stores altogether made the
+  // layer2 / layer3 convs 16-22 % faster, most of it the OTHER workgroup's weight DMA queueing behind these bursts) go through
+  // LDS once more, 32 pixels at a time, and leave as whole 128-byte lines
+  constexpr bool STAGE16 = HIPAC_H16_STAGE16 && !OUTF32 && NSW == 2 && WTN == 64;
+  unsigned char* const Sw16 = Wbuf + W_BYTES + wave * 4096;
+  __builtin_amdgcn_s_barrier();  // every wave has left the K loop: band and ring are free
+  HALO_STAMP(t_bar);
+  {
+    // the next tile's first band chunk and first weight tile(s) land behind this epilogue
+    const int vn = vb + gridDim.x;
+    const int mtn = ((vn >> 3) / NTILES_N) < ((n_mtiles + 7) >> 3) ? (vn & 7) * ((n_mtiles + 7) >> 3) + (vn >> 3) / NTILES_N : n_mtiles;
+    if (mtn < n_mtiles) {
+      if constexpr (S2) {
+        plane_offsets(mtn * BM);
+        issue_plane_band(0, 0);
+      } else {
+        issue_band_of(mtn * BM, 0);
       }
-    };
-    static_for<MT>([&](auto SUB) { load_resid_d(SUB); });
-    __builtin_amdgcn_s_barrier();  // every wave has left the K loop: band and ring are free
-    HALO_STAMP(t_bar);
-    {
-      // the next tile's first band chunk and first weight tile(s) land behind this epilogue
-      const int vn = vb + gridDim.x;
-#if HIPAC_H16_XCD_CHUNKS
-      const int mtn = ((vn >> 3) / NTILES_N) < ((n_mtiles + 7) >> 3) ? (vn & 7) * ((n_mtiles + 7) >> 3) + (vn >> 3) / NTILES_N : n_mtiles;
-#else
-      const int mtn = ((vn >> 3) / NTILES_N) * 8 + (vn & 7);
-#endif
-      if (mtn < n_mtiles) {
-        if constexpr (S2) {
-          plane_offsets(mtn * BM);
-          issue_plane_band(0, 0);
-        } else {
-          issue_band_of(mtn * BM, 0);
-        }
-        const int dn = (((vn >> 3) % NTILES_N) * BN - n0) * KTOT * 2;  // the next tile's weight rows relative to this one's
+      const int dn = (((vn >> 3) % NTILES_N) * BN - n0) * KTOT * 2;  // the next tile's weight rows relative to this one's
 #pragma unroll
-        for (int i = 0; i < WPW; ++i) w_off[i] += dn;
+      for (int i = 0; i < WPW; ++i) w_off[i] += dn;
 #pragma unroll
-        for (int pstep = 0; pstep < NSW - 1; ++pstep)
-          if (pstep < 9 * CC) issue_w(pstep, pstep);
-      }
+      for (int pstep = 0; pstep < NSW - 1; ++pstep)
+        if (pstep < 9 * CC) issue_w(pstep, pstep);
     }
-    HALO_STAMP(t_pref);
+  }
+  HALO_STAMP(t_pref);
 #if HIPAC_H16_EPI_PRIO
-    __builtin_amdgcn_s_setprio(HIPAC_H16_EPI_PRIO);
+  __builtin_amdgcn_s_setprio(HIPAC_H16_EPI_PRIO);
 #endif
-    // pooled epilogue state: S[..][0] = sums of the values rounded to the grid 2^-10, S[..][1] = sums of the remainders rounded
-    // to the grid 2^-29, for the image the walk over the wave's pixels is in
-    [[maybe_unused]] f32x4 poolS[NT][2];
-    [[maybe_unused]] int pool_slot = 0, pool_bound = 0;  // that image's slot; first pixel of the image after it
-    [[maybe_unused]] auto pool_flush = [&](int slot_) {
-      float* dst = reinterpret_cast<float*>(outp) + (((size_t)(mt * WM + wm) * kPoolSlots + slot_) * 2) * COUT + n0 + wn * WTN + 4 * g;
+  // pooled epilogue state: S[..][0] = sums of the values rounded to the grid 2^-10, S[..][1] = sums of the remainders rounded
+  // to the grid 2^-29, for the image the walk over the wave's pixels is in
+  [[maybe_unused]] f32x4 poolS[NT][2];
+  [[maybe_unused]] int pool_slot = 0, pool_bound = 0;  // that image's slot; first pixel of the image after it
+  [[maybe_unused]] auto pool_flush = [&](int slot_) {
+    float* dst = reinterpret_cast<float*>(outp) + (((size_t)(mt * WM + wm) * kPoolSlots + slot_) * 2) * COUT + n0 + wn * WTN + 4 * g;
 #pragma unroll
-      for (int j = 0; j < NT; ++j)
+    for (int j = 0; j < NT; ++j)
 #pragma unroll
-        for (int part = 0; part < 2; ++part) {
-          f32x4 t;
+      for (int part = 0; part < 2; ++part) {
+        f32x4 t;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) t[e] = row16_sum(poolS[j][part][e]);
-          if (n16 == 0) *reinterpret_cast<float4*>(dst + part * COUT + 16 * j) = make_float4(t[0], t[1], t[2], t[3]);
-        }
-    };
+        for (int e = 0; e < 4; ++e) t[e] = row16_sum(poolS[j][part][e]);
+        if (n16 == 0) *reinterpret_cast<float4*>(dst + part * COUT + 16 * j) = make_float4(t[0], t[1], t[2], t[3]);
+      }
+  };
+  if constexpr (POOL) {
+    constexpr int IMG = H * W;
+    const int mwave = m0 + wm * WPX;
+    pool_slot = mwave / IMG - m0 / IMG;
+    pool_bound = (mwave / IMG + 1) * IMG;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) poolS[j][0] = poolS[j][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  static_for<MT>([&](auto SUB) {
+    constexpr int i = decltype(SUB)::value;
+    const int m = mw0 + 16 * i;
     if constexpr (POOL) {
-      constexpr int IMG = H * W;
-      const int mwave = m0 + wm * WPX;
-      pool_slot = mwave / IMG - m0 / IMG;
-      pool_bound = (mwave / IMG + 1) * IMG;
+      // An EXACT sum, so that an image's features do not depend on where in the batch (which lanes, which tile) it sits:
+      // v = hi + lo + r with hi on the grid 2^-10 (v + C - C rounds to the grid of C's ulp), lo = (v - hi) on the grid
+      // 2^-29, |r| <= 2^-30.  Sums of such terms are exact in fp32 while sum(hi) < 2^14 (|lo| <= 2^-11: 49 of them stay
+      // below 2^-5 = 2^24 grid steps), whatever the order -- per-lane sums, the DPP tree, head_pool_kernel.
+      f32x4 hi[NT], lo[NT];
+      const bool live = m < M;
 #pragma unroll
-      for (int j = 0; j < NT; ++j) poolS[j][0] = poolS[j][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    static_for<MT>([&](auto SUB) {
-      constexpr int i = decltype(SUB)::value;
-      const int m = mw0 + 16 * i;
-      if constexpr (POOL) {
-        // An EXACT sum, so that an image's features do not depend on where in the batch (which lanes, which tile) it sits:
-        // v = hi + lo + r with hi on the grid 2^-10 (v + C - C rounds to the grid of C's ulp), lo = (v - hi) on the grid
-        // 2^-29, |r| <= 2^-30.  Sums of such terms are exact in fp32 while sum(hi) < 2^14 (|lo| <= 2^-11: 49 of them stay
-        // below 2^-5 = 2^24 grid steps), whatever the order -- per-lane sums, the DPP tree, head_pool_kernel.
-        f32x4 hi[NT], lo[NT];
-        const bool live = m < M;
+      for (int j = 0; j < NT; ++j) {
+        float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
+        for (int e = 0; e < 4; ++e) {
+          v[e] = live ? fmaxf(v[e], 0.f) : 0.f;
+          hi[j][e] = (v[e] + 12288.0f) - 12288.0f;                       // C = 1.5 x 2^13: ulp 2^-10
+          lo[j][e] = ((v[e] - hi[j][e]) + 0.0234375f) - 0.0234375f;     // C = 1.5 x 2^-6: ulp 2^-29
+        }
+      }
+      if (m0 + wm * WPX + 16 * i + 15 < pool_bound) {  // (uniform) the whole sub-tile lies in the current image
+#pragma unroll
+        for (int j = 0; j < NT; ++j) poolS[j][0] += hi[j], poolS[j][1] += lo[j];
+      } else {  // an image ends inside this sub-tile (or right in front of it): finish it, start the next one
+        const bool in_a = m < pool_bound;
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) poolS[j][0][e] += in_a ? hi[j][e] : 0.f, poolS[j][1][e] += in_a ? lo[j][e] : 0.f;
+        pool_flush(pool_slot);
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) poolS[j][0][e] = in_a ? 0.f : hi[j][e], poolS[j][1][e] = in_a ? 0.f : lo[j][e];
+        ++pool_slot, pool_bound += H * W;
+      }
+      if constexpr (i == MT - 1) {
+        // the image the walk ends in (slot <= kPoolSlots - 1); if the wave's last pixel closed an image, an all-zero set
+        // for a slot nobody reads -- unless it would lie outside the buffer
+        if (pool_slot < kPoolSlots) pool_flush(pool_slot);
+      }
+    } else if constexpr (OUTF32) {
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
+        if constexpr (RELU) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        }
+        if (m < M)
+          *reinterpret_cast<float4*>(reinterpret_cast<float*>(outp) + (size_t)m * COUT + n0 + wn * WTN + 16 * j + 4 * g) =
+              make_float4(v[0], v[1], v[2], v[3]);
+      }
+    } else {
+#pragma unroll
+      for (int jp = 0; jp < NT / 2; ++jp) {
+        unsigned P[2][2];
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          const int j = 2 * jp + jj;
           float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
-          if constexpr (EPI_RESID) {
-            const typename E::vec4 rr = __builtin_bit_cast(typename E::vec4, rq32[i][j]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += (float)rr[e];
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[e] = live ? fmaxf(v[e], 0.f) : 0.f;
-            hi[j][e] = (v[e] + 12288.0f) - 12288.0f;                       // C = 1.5 x 2^13: ulp 2^-10
-            lo[j][e] = ((v[e] - hi[j][e]) + 0.0234375f) - 0.0234375f;     // C = 1.5 x 2^-6: ulp 2^-29
-          }
-        }
-        if (m0 + wm * WPX + 16 * i + 15 < pool_bound) {  // (uniform) the whole sub-tile lies in the current image
-#pragma unroll
-          for (int j = 0; j < NT; ++j) poolS[j][0] += hi[j], poolS[j][1] += lo[j];
-        } else {  // an image ends inside this sub-tile (or right in front of it): finish it, start the next one
-          const bool in_a = m < pool_bound;
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) poolS[j][0][e] += in_a ? hi[j][e] : 0.f, poolS[j][1][e] += in_a ? lo[j][e] : 0.f;
-          pool_flush(pool_slot);
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) poolS[j][0][e] = in_a ? 0.f : hi[j][e], poolS[j][1][e] = in_a ? 0.f : lo[j][e];
-          ++pool_slot, pool_bound += H * W;
-        }
-        if constexpr (i == MT - 1) {
-          // the image the walk ends in (slot <= kPoolSlots - 1); if the wave's last pixel closed an image, an all-zero set
-          // for a slot nobody reads -- unless it would lie outside the buffer
-          if (pool_slot < kPoolSlots) pool_flush(pool_slot);
-        }
-      } else if constexpr (OUTF32) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
-          if constexpr (EPI_RESID) {
-            const typename E::vec4 rr = __builtin_bit_cast(typename E::vec4, rq32[i][j]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += (float)rr[e];
-          }
           if constexpr (RELU) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
           }
-          if (m < M)
-            *reinterpret_cast<float4*>(reinterpret_cast<float*>(outp) + (size_t)m * COUT + n0 + wn * WTN + 16 * j + 4 * g) =
-                make_float4(v[0], v[1], v[2], v[3]);
+          P[jj][0] = PackPair<T>::pack_rn(v[0], v[1]);
+          P[jj][1] = PackPair<T>::pack_rn(v[2], v[3]);
         }
-      } else {
-#pragma unroll
-        for (int jp = 0; jp < NT / 2; ++jp) {
-          unsigned R[4] = {0u, 0u, 0u, 0u};
-          if constexpr (EPI_RESID) {
-            R[0] = rq[i][jp][0], R[1] = rq[i][jp][1], R[2] = rq[i][jp][2], R[3] = rq[i][jp][3];
-            permlane16_swap(R[0], R[2]);  // -> (R[0], R[1]) = this lane's 4 channels of tile 2 jp, (R[2], R[3]) = of tile 2 jp + 1
-            permlane16_swap(R[1], R[3]);
-          }
-          unsigned P[2][2];
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) {
-            const int j = 2 * jp + jj;
-            float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
-            if constexpr (EPI_RESID) {
-              const typename E::vec4 rr = __builtin_bit_cast(typename E::vec4, u32x2{R[2 * jj], R[2 * jj + 1]});
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] += (float)rr[e];
-            }
-            if constexpr (RELU) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            P[jj][0] = PackPair<T>::pack_rn(v[0], v[1]);
-            P[jj][1] = PackPair<T>::pack_rn(v[2], v[3]);
-          }
-          permlane16_swap(P[0][0], P[1][0]);
-          permlane16_swap(P[0][1], P[1][1]);
-          if constexpr (STAGE16) {
-            // through the wave's 4 KB of ring slot 1 (slot 0 is receiving the next tile's first weight tile): [32 px][128 B],
-            // 16-byte position c ^ (px & 7) -- the eight lanes a ds_write_b128 serves together are eight pixels of different
-            // px & 7 (perm16), i.e. eight different positions = all 32 banks
-            const int spx = (i & 1) * 16 + pn;
-            const int sch = 4 * jp + 2 * (g & 1) + (g >> 1);  // the 16-byte chunk of the wave's 128 bytes this lane holds
-            *reinterpret_cast<u32x4*>(Sw16 + spx * 128 + ((sch ^ (spx & 7)) << 4)) = u32x4{P[0][0], P[0][1], P[1][0], P[1][1]};
-          } else if ((HIPAC_H16_ABL & 32) ? m < 0 : m < M)  // (ablation 32: no stores)
-            store16_out<HIPAC_NT_STORES && (H * W >= 784)>(reinterpret_cast<T*>(outp) + (size_t)((HIPAC_H16_ABL & 128) ? (m & 0x3fff) : m) * COUT + c_lane + 32 * jp,
-                                                           u32x4{P[0][0], P[0][1], P[1][0], P[1][1]});  // (ablation 128: every store into one L2-resident window)
-        }
-        if constexpr (STAGE16 && (i & 1)) {
-          // the 32-pixel group is staged: out as whole 128-byte lines -- 8 lanes per pixel, 16 bytes each
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int spx = (lane >> 3) + 8 * k, sch = lane & 7;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(Sw16 + spx * 128 + ((sch ^ (spx & 7)) << 4));
-            const int ms = m0 + wm * WPX + (i >> 1) * 32 + spx;
-            if ((HIPAC_H16_ABL & 32) ? ms < 0 : ms < M)
-              *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(outp) + (size_t)ms * COUT + n0 + wn * WTN + sch * 8) = v;
-          }
-        }
+        permlane16_swap(P[0][0], P[1][0]);
+        permlane16_swap(P[0][1], P[1][1]);
+        if constexpr (STAGE16) {
+          // through the wave's 4 KB of ring slot 1 (slot 0 is receiving the next tile's first weight tile): [32 px][128 B],
+          // 16-byte position c ^ (px & 7) -- the eight lanes a ds_write_b128 serves together are eight pixels of different
+          // px & 7 (perm16), i.e. eight different positions = all 32 banks
+          const int spx = (i & 1) * 16 + pn;
+          const int sch = 4 * jp + 2 * (g & 1) + (g >> 1);  // the 16-byte chunk of the wave's 128 bytes this lane holds
+          *reinterpret_cast<u32x4*>(Sw16 + spx * 128 + ((sch ^ (spx & 7)) << 4)) = u32x4{P[0][0], P[0][1], P[1][0], P[1][1]};
+        } else if ((HIPAC_H16_ABL & 32) ? m < 0 : m < M)  // (ablation 32: no stores)
+          store16_out(reinterpret_cast<T*>(outp) + (size_t)((HIPAC_H16_ABL & 128) ? (m & 0x3fff) : m) * COUT + c_lane + 32 * jp,
+                      u32x4{P[0][0], P[0][1], P[1][0], P[1][1]});  // (ablation 128: every store into one L2-resident window)
       }
-    });
-#ifdef HIPAC_HALO_STAMPS
-    HALO_STAMP(t_end);
-    if (tid == 0) {
-      atomicAdd(&g_halo_stamps[0], t_first - t_start);
-      atomicAdd(&g_halo_stamps[1], t_loop - t_first);
-      atomicAdd(&g_halo_stamps[2], t_end - t_loop);
-      atomicAdd(&g_halo_stamps[3], 1ull);
-      atomicAdd(&g_halo_stamps[4], t_bar - t_loop);
-      atomicAdd(&g_halo_stamps[5], t_pref - t_bar);
-      atomicAdd(&g_halo_stamps[6], t_end - t_pref);
-      atomicAdd(&g_halo_stamps[7], t_setup - t_start);
-    }
-#endif
-#if HIPAC_H16_EPI_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    prev_full = !POOL && (m0 + BM <= M);  // (POOL: the number of stores depends on the images the tile meets)
-    continue;  // next tile
-  }
-  // the residual of the first 32-pixel group is requested here, not from inside the last K step as in the 32x32 kernel: its
-  // 16 registers do not fit beside the K loop's, and the latency has the barrier, the band prefetch and the staging round
-  // trip of group 0 to hide behind
-  load_resid(std::integral_constant<int, 0>{});
-  const float4 b_lo = *reinterpret_cast<const float4*>(bias + e_c0);
-  const float4 b_hi = *reinterpret_cast<const float4*>(bias + e_c0 + 4);
-  __builtin_amdgcn_s_barrier();  // every wave has left the K loop: band and ring are free
-  HALO_STAMP(t_bar);
-  {
-    // prefetch the next tile's first band chunk; it lands behind this epilogue
-    const int vn = vb + gridDim.x;
-#if HIPAC_H16_XCD_CHUNKS
-    const int mtn = ((vn >> 3) / NTILES_N) < ((n_mtiles + 7) >> 3) ? (vn & 7) * ((n_mtiles + 7) >> 3) + (vn >> 3) / NTILES_N : n_mtiles;
-#else
-    const int mtn = ((vn >> 3) / NTILES_N) * 8 + (vn & 7);
-#endif
-    if (mtn < n_mtiles) issue_band_of(mtn * BM, 0);
-  }
-  HALO_STAMP(t_pref);
-  unsigned char* const Sl = Wbuf + wave * (32 * SROWW);  // this wave's private staging
-  static_for<G32>([&](auto SUB) {
-    constexpr int i = decltype(SUB)::value;
-    if constexpr (i + 1 < G32) load_resid(std::integral_constant<int, i + 1>{});
-    // accumulators -> fp32 rows: sub-tiles 2i (staging pixels 0-15) and 2i+1 (16-31); a lane holds channels 4g .. 4g+3 of
-    // every 16-wide tile of pixel pn (LDS operations of one wave complete in order: no barrier)
+      if constexpr (STAGE16 && (i & 1)) {
+        // the 32-pixel group is staged: out as whole 128-byte lines -- 8 lanes per pixel, 16 bytes each
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        *reinterpret_cast<f32x4*>(Sl + (hh * 16 + pn) * SROWW + (j * 16 + 4 * g) * 4) = acc[2 * i + hh][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-      const int px = e_px + k * (64 / CPW);
-      const int m = m0 + wm * WPX + i * 32 + px;
-      const f32x4 lo = *reinterpret_cast<const f32x4*>(Sl + px * SROWW + (lane % CPW) * 32);
-      const f32x4 hi = *reinterpret_cast<const f32x4*>(Sl + px * SROWW + (lane % CPW) * 32 + 16);
-      if (m < M) {
-        float v[8] = {lo[0] + b_lo.x, lo[1] + b_lo.y, lo[2] + b_lo.z, lo[3] + b_lo.w,
-                      hi[0] + b_hi.x, hi[1] + b_hi.y, hi[2] + b_hi.z, hi[3] + b_hi.w};
-        const size_t o = (size_t)m * COUT + e_c0;
-        if constexpr (RESID) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += (float)rv[i & 1][k][e];
-        }
-        if constexpr (RELU) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if constexpr (OUTF32) {
-          float* op = reinterpret_cast<float*>(outp) + o;
-          *reinterpret_cast<float4*>(op) = make_float4(v[0], v[1], v[2], v[3]);
-          *reinterpret_cast<float4*>(op + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        } else {
-          frag ov;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ov[e] = (T)v[e];
-          *reinterpret_cast<frag*>(reinterpret_cast<T*>(outp) + o) = ov;
+        for (int k = 0; k < 4; ++k) {
+          const int spx = (lane >> 3) + 8 * k, sch = lane & 7;
+          const u32x4 v = *reinterpret_cast<const u32x4*>(Sw16 + spx * 128 + ((sch ^ (spx & 7)) << 4));
+          const int ms = m0 + wm * WPX + (i >> 1) * 32 + spx;
+          if ((HIPAC_H16_ABL & 32) ? ms < 0 : ms < M)
+            *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(outp) + (size_t)ms * COUT + n0 + wn * WTN + sch * 8) = v;
         }
       }
     }
-    // the next group overwrites the staging rows: this wave's reads above must have returned
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   });
 #ifdef HIPAC_HALO_STAMPS
   HALO_STAMP(t_end);
   if (tid == 0) {
-    atomicAdd(&g_halo_stamps[0], t_first - t_start);  // prologue: band + first weight tile in flight
-    atomicAdd(&g_halo_stamps[1], t_loop - t_first);   // K loop
-    atomicAdd(&g_halo_stamps[2], t_end - t_loop);     // epilogue (all of it)
+    atomicAdd(&g_halo_stamps[0], t_first - t_start);
+    atomicAdd(&g_halo_stamps[1], t_loop - t_first);
+    atomicAdd(&g_halo_stamps[2], t_end - t_loop);
     atomicAdd(&g_halo_stamps[3], 1ull);
-    atomicAdd(&g_halo_stamps[4], t_bar - t_loop);     // ... of which: waiting for the other waves to leave the K loop
-    atomicAdd(&g_halo_stamps[5], t_pref - t_bar);     // ... issuing the next tile's band
-    atomicAdd(&g_halo_stamps[6], t_end - t_pref);     // ... the staged groups
+    atomicAdd(&g_halo_stamps[4], t_bar - t_loop);
+    atomicAdd(&g_halo_stamps[5], t_pref - t_bar);
+    atomicAdd(&g_halo_stamps[6], t_end - t_pref);
+    atomicAdd(&g_halo_stamps[7], t_setup - t_start);
   }
 #endif
+#if HIPAC_H16_EPI_PRIO
+  __builtin_amdgcn_s_setprio(0);
+#endif
+  prev_full = !POOL && (m0 + BM <= M);  // (POOL: the number of stores depends on the images the tile meets)
   }  // persistent tile loop
 }
 

@@ -62,13 +62,12 @@ Plan make_plan(int batch, int precision) {
   int gc_cap = env_int("HIPAC_GROUP", 4096, 1, 8192);
   // fp16q8: halo16x2.h addresses its pair tensors with 32-bit byte offsets (buffer descriptors): layer3's stride-2 entry conv sees
   // 4 x gc x 196 pixels x 128 channels x 4 bytes, which stays below 2^31 up to gc = 5 349
-  if ((precision == HIPAC_PREC_FP16Q8 || (precision == HIPAC_PREC_FP16X3 && x3_on_halo16())) && gc_cap > 4096) gc_cap = 4096;
+  if (pair_mode(precision) && gc_cap > 4096) gc_cap = 4096;
   p.fuse_stem = wide_mode(precision) ? 0 : env_int("HIPAC_FUSE_STEM", 1, 0, 1);
   p.u8_input = 0;
   p.stem_strip = env_int("HIPAC_STEM_STRIP", 1, 0, 1);
   p.l1_fused = wide_mode(precision) ? 0 : env_int("HIPAC_L1_FUSED", 1, 0, 1);
-  const bool on_halo16x2 = precision == HIPAC_PREC_FP16Q8 || (precision == HIPAC_PREC_FP16X3 && x3_on_halo16());
-  p.pool_head = ((wide_mode(precision) && !on_halo16x2) || !halo_pool_compiled()) ? 0 : env_int("HIPAC_POOL_HEAD", 1, 0, 1);
+  p.pool_head = precision == HIPAC_PREC_FP32 ? 0 : env_int("HIPAC_POOL_HEAD", 1, 0, 1);
   if (batch < 1) batch = 1;
   p.bc = batch < bc_cap ? batch : bc_cap;
   p.gc = batch < gc_cap ? batch : gc_cap;
@@ -346,40 +345,6 @@ static int pack_conv(const hipac_convbn_t& c, int cout, int cin, int ks, float e
   return upload(bias.data(), bias.size() * 4, (void**)&out->bias);
 }
 
-// fp16x3: BN folded as in pack_conv, every weight split into hi = rn16(v), lo = rn16(v - hi); K order per tap =
-// 64-channel triples (hi_c | lo_c | hi_c) matching the activation chunks (hi_c, hi_c, lo_c) of the kernels' K loop
-// (conv_igemm.h, conv_glds_kernel's SPLIT note).
-static int pack_conv_split(const hipac_convbn_t& c, int cout, int cin, int ks, float eps, ConvW* out) {
-  HIPAC_REQUIRE(c.conv_w && c.bn_gamma && c.bn_beta && c.bn_mean && c.bn_var, HIPAC_EINVAL,
-                "pack: null tensor pointer (cout=%d cin=%d ks=%d)", cout, cin, ks);
-  HIPAC_REQUIRE(cin % 64 == 0, HIPAC_EINVAL, "pack: split layout needs cin %% 64 == 0 (%d)", cin);
-  const int K = ks * ks * 3 * cin;
-  std::vector<uint16_t> w((size_t)cout * K, 0);
-  std::vector<float> bias(cout);
-  for (int o = 0; o < cout; ++o) {
-    const double scale = (double)c.bn_gamma[o] / sqrt((double)c.bn_var[o] + (double)eps);
-    bias[o] = (float)((double)c.bn_beta[o] - (double)c.bn_mean[o] * scale);
-    for (int i = 0; i < cin; ++i)
-      for (int kh = 0; kh < ks; ++kh)
-        for (int kw = 0; kw < ks; ++kw) {
-          const float v = (float)((double)c.conv_w[(((size_t)o * cin + i) * ks + kh) * ks + kw] * scale);
-          const uint16_t hb = f32_to_f16_bits(v);
-          _Float16 hh;
-          memcpy(&hh, &hb, 2);
-          const uint16_t lb = f32_to_f16_bits(v - (float)hh);
-          uint16_t* row = &w[(size_t)o * K + ((size_t)kh * ks + kw) * 3 * cin + (size_t)(i / 64) * 192 + (i % 64)];
-          row[0] = hb;
-          row[64] = lb;
-          row[128] = hb;
-        }
-  }
-  int rc = upload(w.data(), w.size() * 2, &out->w);
-  if (rc) return rc;
-  return upload(bias.data(), bias.size() * 4, (void**)&out->bias);
-}
-
-static int pack_conv_split3(const hipac_convbn_t& c, int cout, int cin, float eps, ConvW* out) { return pack_conv_split(c, cout, cin, 3, eps, out); }
-
 // fp16q8, 3x3 / stride 1 convs (halo16x2.h): BN folded, every weight split into the fp16 pair (hi, lo); per output channel and tap,
 // per 64-channel chunk 256 bytes: [hi: 64 fp16 | e4m3(hi * 2^4): 64 | e4m3(lo * 2^15): 64]
 // (q8 = false: fp16x3 on the same kernel -- the second 128 bytes of a chunk are the 64 lo halves as fp16)
@@ -601,15 +566,13 @@ int hipac_resnet18_pack(const hipac_resnet18_params_t* params, int precision, hi
   const int ch[4] = {64, 128, 256, 512};
   for (int s = 0; s < 4 && !rc && split; ++s) {
     const int cin = s == 0 ? 64 : ch[s - 1];
-    const bool rows = q8 || x3_on_halo16();  // halo16x2.h's weight rows
-    auto pack3 = q8 ? pack_conv_q8_3x3 : rows ? pack_conv_x3rows_3x3 : pack_conv_split3;
+    auto pack3 = q8 ? pack_conv_q8_3x3 : pack_conv_x3rows_3x3;  // halo16x2.h's weight rows
     rc = pack3(params->block[2 * s][0], ch[s], cin, eps, &w->net.block[2 * s][0]);
     if (!rc) rc = pack3(params->block[2 * s][1], ch[s], ch[s], eps, &w->net.block[2 * s][1]);
     if (!rc) rc = pack3(params->block[2 * s + 1][0], ch[s], ch[s], eps, &w->net.block[2 * s + 1][0]);
     if (!rc) rc = pack3(params->block[2 * s + 1][1], ch[s], ch[s], eps, &w->net.block[2 * s + 1][1]);
     if (!rc && s > 0)
-      rc = rows ? pack_conv_q8(params->down[s - 1], ch[s], cin, eps, &w->net.down[s - 1], 1, q8)  // (folded into conv2: halo16x2.h, PCIN)
-                : pack_conv_split(params->down[s - 1], ch[s], cin, 1, eps, &w->net.down[s - 1]);
+      rc = pack_conv_q8(params->down[s - 1], ch[s], cin, eps, &w->net.down[s - 1], 1, q8);  // (folded into conv2: halo16x2.h, PCIN)
   }
   for (int s = 0; s < 4 && !rc && !split; ++s) {
     const int cin = s == 0 ? 64 : ch[s - 1];
@@ -619,7 +582,7 @@ int hipac_resnet18_pack(const hipac_resnet18_params_t* params, int precision, hi
     if (!rc) rc = pack_conv(params->block[2 * s + 1][1], ch[s], ch[s], 3, eps, precision, false, &w->net.block[2 * s + 1][1]);
     if (!rc && s > 0) rc = pack_conv(params->down[s - 1], ch[s], cin, 1, eps, precision, false, &w->net.down[s - 1]);
   }
-  for (int st = 1; st < 4 && !rc && (!wide_mode(precision) || q8 || (split && x3_on_halo16())); ++st) {
+  for (int st = 1; st < 4 && !rc && precision != HIPAC_PREC_FP32; ++st) {
     // block0.conv2's bias + the projection's, for the kernel that accumulates both into one accumulator
     const hipac_convbn_t& a = params->block[2 * st][1];
     const hipac_convbn_t& b = params->down[st - 1];

@@ -7,7 +7,7 @@
 //             global average pool.  Pre-BN and post-activation maps of every conv are kept for the backward.
 //   backward  BN backward (two passes: d gamma / d beta, then dx), conv weight gradient (MFMA GEMM over the
 //             pixel axis, split-K with fp32 atomics), conv data gradient = the forward kernel on flipped /
-//             transposed weights (stride-2 layers: on the zero-interleaved gradient), max-pool / average-pool
+//             transposed weights (stride-2 layers: by parity class), max-pool / average-pool
 //             backward, ReLU masks fused into the consumers.
 //   plus      linear layers (projector, fc) on a strided fp32 MFMA GEMM, weighted cross-entropy, Adam.
 //
@@ -35,7 +35,7 @@ struct TrainPlan {
   size_t wgrad_p;           // packed weight-gradient accumulator (largest conv)
   size_t zero_bias;         // float[512] zeros
   size_t g[3];              // gradient maps (largest activation each)
-  size_t up;                // zero-interleaved gradient of a stride-2 layer
+  size_t up;                // gradient through a 1x1 / stride-2 projection, on the fine grid
   size_t total;
 };
 
@@ -335,23 +335,6 @@ __global__ __launch_bounds__(256) void add_mask_kernel(const float* __restrict__
       v.x = k.x > 0.f ? v.x : 0.f, v.y = k.y > 0.f ? v.y : 0.f, v.z = k.z > 0.f ? v.z : 0.f, v.w = k.w > 0.f ? v.w : 0.f;
     }
     *reinterpret_cast<float4*>(out + i * 4) = v;
-  }
-}
-
-// zero-interleave: up[b][2y][2x][c] = g[b][y][x][c], every other position 0 (up is H2 x H2, H2 = 2 * H)
-__global__ __launch_bounds__(256) void upsample_zero_kernel(const float* __restrict__ g, float* __restrict__ up,
-                                                            long long n4, int H, int C) {
-  const int c4 = C >> 2, H2 = 2 * H;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    const int cg = (int)(i % c4);
-    long long t = i / c4;
-    const int X = (int)(t % H2);
-    t /= H2;
-    const int Y = (int)(t % H2);
-    const long long b = t / H2;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!(X & 1) && !(Y & 1)) v = *reinterpret_cast<const float4*>(g + (((b * H + (Y >> 1)) * H + (X >> 1)) * C) + 4 * cg);
-    *reinterpret_cast<float4*>(up + i * 4) = v;
   }
 }
 
@@ -737,35 +720,17 @@ static int conv_forward(int i, const float* in, const float* wp, const float* zb
     default: return conv_f32<256, 512, 14, 1, 2>(in, wp, zb, out, n, s);
   }
 }
-// data gradient of conv i: g (gradient wrt the conv output; stride-2 layers: already zero-interleaved to hin x hin)
-// -> gradient wrt the conv input, with weights packed in mode 1
+// data gradient of a 3x3 / stride 1 conv i: g (gradient wrt the conv output) -> gradient wrt the conv input, with weights packed
+// in mode 1 (stride-2 convs: conv_dgrad_s2)
 static int conv_dgrad(int i, const float* g, const float* wd, const float* zb, float* out, int n, hipStream_t s) {
-  const ConvDesc& d = kConvs[i];
-  if (d.ks == 3 && d.stride == 1) {
-    switch (d.cout) {
-      case 64: return conv_f32<64, 64, 56, 3, 1>(g, wd, zb, out, n, s);
-      case 128: return conv_f32<128, 128, 28, 3, 1>(g, wd, zb, out, n, s);
-      case 256: return conv_f32<256, 256, 14, 3, 1>(g, wd, zb, out, n, s);
-      default: return conv_f32<512, 512, 7, 3, 1>(g, wd, zb, out, n, s);
-    }
-  }
-  if (d.ks == 3) {
-    switch (d.cout) {
-      case 128: return conv_f32<128, 64, 56, 3, 1>(g, wd, zb, out, n, s);
-      case 256: return conv_f32<256, 128, 28, 3, 1>(g, wd, zb, out, n, s);
-      default: return conv_f32<512, 256, 14, 3, 1>(g, wd, zb, out, n, s);
-    }
-  }
-  switch (d.cout) {
-    case 128: return conv_f32<128, 64, 56, 1, 1>(g, wd, zb, out, n, s);
-    case 256: return conv_f32<256, 128, 28, 1, 1>(g, wd, zb, out, n, s);
-    default: return conv_f32<512, 256, 14, 1, 1>(g, wd, zb, out, n, s);
+  switch (kConvs[i].cout) {
+    case 64: return conv_f32<64, 64, 56, 3, 1>(g, wd, zb, out, n, s);
+    case 128: return conv_f32<128, 128, 28, 3, 1>(g, wd, zb, out, n, s);
+    case 256: return conv_f32<256, 256, 14, 3, 1>(g, wd, zb, out, n, s);
+    default: return conv_f32<512, 512, 7, 3, 1>(g, wd, zb, out, n, s);
   }
 }
 
-#ifndef HIPAC_F32_DGRAD_CLASSES
-#define HIPAC_F32_DGRAD_CLASSES 1  // stride-2 data gradients by parity class (a quarter of the MFMAs); 0: the zero-interleaved form
-#endif
 // data gradient of a STRIDE-2 conv i by parity classes: g on the coarse grid, weights in mode 3 (3x3) or 1 (1x1; `out` zeroed)
 static int conv_dgrad_s2(int i, const float* g, const float* wd, const float* zb, float* out, int n, hipStream_t s) {
   const ConvDesc& d = kConvs[i];
@@ -1020,40 +985,22 @@ int hipac_train_encoder_backward(const float* params, const float* dfeats, int b
       TRY(conv_dgrad(c2, gB, wd, zb, gC, n, s));                                       // gC = d post(c1) (before its ReLU mask)
       TRY(bn_backward(c, c1, n, gC, post(c1), gC, grads, accumulate));                 // gC = d pre(c1)
       TRY(conv_wgrad(c, c1, n, xin_blk, gC, grads, accumulate));
-      if (d1.stride == 2 && HIPAC_F32_DGRAD_CLASSES) {
+      if (d1.stride == 2) {
         TRY(pack_weights(params + param_offset(c1), wd, c1, 3, s));
         TRY(conv_dgrad_s2(c1, gC, wd, zb, gB, n, s));                                  // gB = d block input via the main path
       } else {
         TRY(pack_weights(params + param_offset(c1), wd, c1, 1, s));
-        const float* g1 = gC;
-        if (d1.stride == 2) {
-          const long long nu4 = (long long)n * d1.hin * d1.hin * d1.cout / 4;
-          hipLaunchKernelGGL(upsample_zero_kernel, dim3(grid_for(nu4)), dim3(256), 0, s, (const float*)gC, up, nu4, d1.hout, d1.cout);
-          TRY((int)hipGetLastError());
-          g1 = up;
-        }
-        TRY(conv_dgrad(c1, g1, wd, zb, gB, n, s));                                     // gB = d block input via the main path
+        TRY(conv_dgrad(c1, gC, wd, zb, gB, n, s));                                     // gB = d block input via the main path
       }
       // --- identity path
       if (down) {
         TRY(bn_backward(c, ds, n, gA, nullptr, gC, grads, accumulate));                // gC = d pre(ds)
         TRY(conv_wgrad(c, ds, n, xin_blk, gC, grads, accumulate));
         TRY(pack_weights(params + param_offset(ds), wd, ds, 1, s));
-        if (HIPAC_F32_DGRAD_CLASSES) {
-          // 1x1 / stride 2: only the even positions of the fine grid receive a gradient; `up` takes it (gC holds the input)
-          HIPAC_CHECK_HIP(hipMemsetAsync(up, 0, (size_t)n * d1.hin * d1.hin * kConvs[ds].cin * 4, s));
-          TRY(conv_dgrad_s2(ds, gC, wd, zb, up, n, s));
-          hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n_in4)), dim3(256), 0, s, (const float*)gB, (const float*)up, prev_post,
-                             gA, n_in4);
-          TRY((int)hipGetLastError());
-          continue;
-        }
-        const long long nu4 = (long long)n * d1.hin * d1.hin * kConvs[ds].cout / 4;
-        hipLaunchKernelGGL(upsample_zero_kernel, dim3(grid_for(nu4)), dim3(256), 0, s, (const float*)gC, up, nu4, kConvs[ds].hout,
-                           kConvs[ds].cout);
-        TRY((int)hipGetLastError());
-        TRY(conv_dgrad(ds, up, wd, zb, gC, n, s));                                     // gC = d block input via the projection
-        hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n_in4)), dim3(256), 0, s, (const float*)gB, (const float*)gC, prev_post,
+        // 1x1 / stride 2: only the even positions of the fine grid receive a gradient; `up` takes it (gC holds the input)
+        HIPAC_CHECK_HIP(hipMemsetAsync(up, 0, (size_t)n * d1.hin * d1.hin * kConvs[ds].cin * 4, s));
+        TRY(conv_dgrad_s2(ds, gC, wd, zb, up, n, s));
+        hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n_in4)), dim3(256), 0, s, (const float*)gB, (const float*)up, prev_post,
                            gA, n_in4);
       } else {
         hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n_in4)), dim3(256), 0, s, (const float*)gB, (const float*)gA, prev_post,

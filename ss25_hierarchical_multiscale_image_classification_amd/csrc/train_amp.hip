@@ -9,7 +9,7 @@
 //             bias and no ReLU; batch statistics from the fp16 map in fp64, two-stage and DETERMINISTIC (per
 //             workgroup partials, summed in a fixed order); normalise (+ residual) (+ ReLU) fp16 -> fp16.
 //   backward  BN backward (same two-stage reductions), data gradient = the same convolution kernels on flipped /
-//             transposed fp16 weights (stride 2: on the zero-interleaved gradient), weight gradient = wgrad_f16_kernel
+//             transposed fp16 weights (stride 2: by parity class), weight gradient = wgrad_f16_kernel
 //             below: an MFMA GEMM over the pixel axis whose operands (dY and X, both [pixel][channel] in memory) are
 //             read TRANSPOSED from LDS by ds_read_b64_tr_b16, split-K partials in fp32 summed in a fixed order (no
 //             atomics: a step run twice gives the same bits).
@@ -43,7 +43,7 @@ struct AmpPlan {
   size_t wpack, wpack_d;    // h16 packed forward weights (all convs) / data-gradient weights (largest conv)
   size_t wg_part;           // float split-K partials of one weight gradient
   size_t zero_bias, zero_page;
-  size_t g[3], up;          // h16 gradient maps, zero-interleaved gradient
+  size_t g[3], up;          // h16 gradient maps, gradient through a 1x1 / stride-2 projection on the fine grid
   size_t total;
 };
 constexpr size_t kWgPartBytes = (size_t)160 << 20;
@@ -328,23 +328,6 @@ __global__ __launch_bounds__(256) void add_mask_h_kernel(const h16* __restrict__
       for (int k = 0; k < 8; ++k) v[k] = m[k] > 0.f ? v[k] : 0.f;
     }
     st8(out + i * 8, v);
-  }
-}
-
-// zero-interleave: up[b][2y][2x][c] = g[b][y][x][c], every other position 0
-__global__ __launch_bounds__(256) void upsample_zero_h_kernel(const h16* __restrict__ g, h16* __restrict__ up, long long n8, int H,
-                                                              int C) {
-  const int c8 = C >> 3, H2 = 2 * H;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    const int cg = (int)(i % c8);
-    long long t = i / c8;
-    const int X = (int)(t % H2);
-    t /= H2;
-    const int Y = (int)(t % H2);
-    const long long b = t / H2;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (!(X & 1) && !(Y & 1)) v = *reinterpret_cast<const u32x4*>(g + (((b * H + (Y >> 1)) * H + (X >> 1)) * C) + 8 * cg);
-    *reinterpret_cast<u32x4*>(up + i * 8) = v;
   }
 }
 
@@ -678,9 +661,6 @@ static int conv_forward_h(int i, const h16* in, const h16* wp, const float* zb, 
     default: return conv_h<256, 512, 14, 1, 2>(in, wp, zb, out, n, s, zp);
   }
 }
-#ifndef HIPAC_AMP_DGRAD_CLASSES
-#define HIPAC_AMP_DGRAD_CLASSES 1  // stride-2 data gradients by parity class (1/4 of the MFMAs, no zero-interleaved map); 0: round-3 first form
-#endif
 // data gradient of a STRIDE-2 conv i by parity classes: g = gradient wrt the conv output on the coarse grid, weights in mode 3
 // (3x3) or mode 1 (1x1; `out` zeroed by the caller)
 static int conv_dgrad_s2_h(int i, const h16* g, const h16* wd, const float* zb, h16* out, int n, hipStream_t s, const char* zp) {
@@ -698,28 +678,13 @@ static int conv_dgrad_s2_h(int i, const h16* g, const h16* wd, const float* zb, 
     default: return launch_dgrad_s2<h16, 512, 256, 7, false>(g, wd, zb, out, n, s, zp);
   }
 }
-// data gradient of conv i: g = gradient wrt the conv output (stride 2: already zero-interleaved to hin x hin), weights in mode 1
+// data gradient of a 3x3 / stride 1 conv i: g = gradient wrt the conv output, weights in mode 1 (stride-2 convs: conv_dgrad_s2_h)
 static int conv_dgrad_h(int i, const h16* g, const h16* wd, const float* zb, h16* out, int n, hipStream_t s, const char* zp) {
-  const ConvDesc& d = kConvs[i];
-  if (d.ks == 3 && d.stride == 1) {
-    switch (d.cout) {
-      case 64: return conv_h<64, 64, 56, 3, 1>(g, wd, zb, out, n, s, zp);
-      case 128: return conv_h<128, 128, 28, 3, 1>(g, wd, zb, out, n, s, zp);
-      case 256: return conv_h<256, 256, 14, 3, 1>(g, wd, zb, out, n, s, zp);
-      default: return conv_h<512, 512, 7, 3, 1>(g, wd, zb, out, n, s, zp);
-    }
-  }
-  if (d.ks == 3) {
-    switch (d.cout) {
-      case 128: return conv_h<128, 64, 56, 3, 1>(g, wd, zb, out, n, s, zp);
-      case 256: return conv_h<256, 128, 28, 3, 1>(g, wd, zb, out, n, s, zp);
-      default: return conv_h<512, 256, 14, 3, 1>(g, wd, zb, out, n, s, zp);
-    }
-  }
-  switch (d.cout) {
-    case 128: return conv_h<128, 64, 56, 1, 1>(g, wd, zb, out, n, s, zp);
-    case 256: return conv_h<256, 128, 28, 1, 1>(g, wd, zb, out, n, s, zp);
-    default: return conv_h<512, 256, 14, 1, 1>(g, wd, zb, out, n, s, zp);
+  switch (kConvs[i].cout) {
+    case 64: return conv_h<64, 64, 56, 3, 1>(g, wd, zb, out, n, s, zp);
+    case 128: return conv_h<128, 128, 28, 3, 1>(g, wd, zb, out, n, s, zp);
+    case 256: return conv_h<256, 256, 14, 3, 1>(g, wd, zb, out, n, s, zp);
+    default: return conv_h<512, 512, 7, 3, 1>(g, wd, zb, out, n, s, zp);
   }
 }
 
@@ -954,39 +919,21 @@ int hipac_train_amp_encoder_backward(const float* params, const float* dfeats, i
       TRY(conv_dgrad_h(c2, gB, wd, zb, gC, n, s, zp));
       TRY(bn_backward_h(c, c1, n, gC, post(c1), gC, grads, accumulate));
       TRY(conv_wgrad_h(c, c1, n, xin_blk, gC, grads, accumulate));
-      if (d1.stride == 2 && HIPAC_AMP_DGRAD_CLASSES) {
+      if (d1.stride == 2) {
         TRY(pack_weights_h(params + param_offset(c1), wd, c1, 3, s));
         TRY(conv_dgrad_s2_h(c1, gC, wd, zb, gB, n, s, zp));
       } else {
         TRY(pack_weights_h(params + param_offset(c1), wd, c1, 1, s));
-        const h16* g1 = gC;
-        if (d1.stride == 2) {
-          const long long nu8 = (long long)n * d1.hin * d1.hin * d1.cout / 8;
-          hipLaunchKernelGGL(upsample_zero_h_kernel, dim3(grid_for(nu8)), dim3(256), 0, s, (const h16*)gC, up, nu8, d1.hout, d1.cout);
-          TRY((int)hipGetLastError());
-          g1 = up;
-        }
-        TRY(conv_dgrad_h(c1, g1, wd, zb, gB, n, s, zp));
+        TRY(conv_dgrad_h(c1, gC, wd, zb, gB, n, s, zp));
       }
       if (down) {
         TRY(bn_backward_h(c, ds, n, gA, nullptr, gC, grads, accumulate));
         TRY(conv_wgrad_h(c, ds, n, xin_blk, gC, grads, accumulate));
         TRY(pack_weights_h(params + param_offset(ds), wd, ds, 1, s));
-        if (HIPAC_AMP_DGRAD_CLASSES) {
-          // 1x1 / stride 2: only the even positions of the fine grid receive a gradient; `up` takes it (gC holds the input)
-          HIPAC_CHECK_HIP(hipMemsetAsync(up, 0, (size_t)n * d1.hin * d1.hin * kConvs[ds].cin * 2, s));
-          TRY(conv_dgrad_s2_h(ds, gC, wd, zb, up, n, s, zp));
-          hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n_in8)), dim3(256), 0, s, (const h16*)gB, (const h16*)up, prev_post, gA,
-                             n_in8);
-          TRY((int)hipGetLastError());
-          continue;
-        }
-        const long long nu8 = (long long)n * d1.hin * d1.hin * kConvs[ds].cout / 8;
-        hipLaunchKernelGGL(upsample_zero_h_kernel, dim3(grid_for(nu8)), dim3(256), 0, s, (const h16*)gC, up, nu8, kConvs[ds].hout,
-                           kConvs[ds].cout);
-        TRY((int)hipGetLastError());
-        TRY(conv_dgrad_h(ds, up, wd, zb, gC, n, s, zp));
-        hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n_in8)), dim3(256), 0, s, (const h16*)gB, (const h16*)gC, prev_post, gA,
+        // 1x1 / stride 2: only the even positions of the fine grid receive a gradient; `up` takes it (gC holds the input)
+        HIPAC_CHECK_HIP(hipMemsetAsync(up, 0, (size_t)n * d1.hin * d1.hin * kConvs[ds].cin * 2, s));
+        TRY(conv_dgrad_s2_h(ds, gC, wd, zb, up, n, s, zp));
+        hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n_in8)), dim3(256), 0, s, (const h16*)gB, (const h16*)up, prev_post, gA,
                            n_in8);
       } else {
         hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n_in8)), dim3(256), 0, s, (const h16*)gB, (const h16*)gA, prev_post, gA,

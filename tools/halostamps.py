@@ -1,4 +1,5 @@
-"""Developer tool (GPU box): phase breakdown of conv3x3_halo_kernel from a -DHIPAC_HALO_STAMPS build.
+"""Developer tool (GPU box): phase breakdown of conv3x3_halo16_kernel (layers 2-4) and the
+layer1 conv kernel from a -DHIPAC_HALO_STAMPS build.
 usage: HIPAC_LIB_NAME=libhipac_stamps.so python tools/halostamps.py"""
 import ctypes
 import os
@@ -31,7 +32,7 @@ for i, name in enumerate(names):
     tot = max(1, buf[0] + buf[1] + buf[2])
     print(f"{name}: workgroups {buf[3]}  per workgroup (s_memtime = shader cycles): prologue {buf[0]/n:.0f}  "
           f"K loop {buf[1]/n:.0f}  epilogue {buf[2]/n:.0f}   shares {buf[0]/tot:.2f} / {buf[1]/tot:.2f} / {buf[2]/tot:.2f}"
-          + (f"   epilogue = barrier {buf[4]/n:.0f} + next band issue {buf[5]/n:.0f} + staged groups {buf[6]/n:.0f}" if buf[6] else "")
+          + (f"   epilogue = barrier {buf[4]/n:.0f} + next band issue {buf[5]/n:.0f} + stores {buf[6]/n:.0f}" if buf[6] else "")
           + (f"   prologue = setup {buf[7]/n:.0f} + wait for DMA / other waves {(buf[0]-buf[7])/n:.0f}" if buf[7] else ""))
 
 for i, name in enumerate(names):
