@@ -7,5 +7,5 @@ Import is cheap and GPU-free; the shared library is loaded on first use
 (``capi.load_library()``) and its absence is an error, never a silent CPU fallback.
 """
 __all__ = ["capi", "synth", "weights", "resnet", "simclr", "patch_dataset", "simclr_dataset", "extract",
-           "features", "dist", "main", "train", "transforms", "build"]
+           "features", "froc", "dist", "main", "train", "transforms", "build"]
 __version__ = "0.1.0"

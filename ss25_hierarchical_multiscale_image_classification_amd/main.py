@@ -17,7 +17,11 @@ tree), ``--precision {bf16,fp16,fp16x3,fp16q8,fp32}``, ``--weights PATH``, ``--s
 nn.DataParallel, src/main.py:481-482, :841-842: ``--patch`` / ``--extract_features`` shard the
 slides, ``--train*`` the batches; started by this program itself before it touches a GPU).
 
-Everything outside the hot path (download, FROC, plots, MIL) is out of scope and the
+``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by
+``features.save_froc_csv``) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
+evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
+
+Everything else outside the hot path (download, plots, MIL) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
 """
 from __future__ import annotations
@@ -30,7 +34,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-OUT_OF_SCOPE = ("download", "remote", "prepare", "validation", "validate", "evaluate", "run_evaluation",
+OUT_OF_SCOPE = ("download", "remote", "prepare", "validation", "validate", "evaluate",
                 "balance_dataset", "count_tumor_patches", "patch_one_slide", "slide", "move_files",
                 "check_good_downloaded_files")
 
@@ -45,6 +49,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--train_strategy", action="store_true", help="Train with a specific strategy")
     p.add_argument("--strategy", type=str, default="self_supervised",
                    choices=["balanced", "weighted_loss", "self_supervised"])
+    p.add_argument("--run_evaluation", action="store_true",
+                   help="CAMELYON16 FROC evaluation of the detection CSVs (src/main.py:1168-1225)")
     for name in OUT_OF_SCOPE:
         if name in ("patch_one_slide", "slide"):
             p.add_argument(f"--{name}", type=str, default=None, help="(reference flag; out of scope here)")
@@ -270,6 +276,16 @@ def cmd_train(args, strategy: Optional[str]):
     return 0
 
 
+def cmd_run_evaluation(args):
+    from .dist import rank_world
+    from .froc import run_evaluation
+
+    rank, _ = rank_world()
+    if rank != 0:  # the evaluation is not sharded: rank 0 does it
+        return 0
+    return run_evaluation(data_root(args))
+
+
 def _seed_everything(seed: int):
     import random
 
@@ -332,6 +348,8 @@ def _dispatch(args) -> int:
         rc = cmd_train(args, None) or rc
     if args.train_strategy:
         rc = cmd_train(args, args.strategy) or rc
+    if args.run_evaluation:
+        rc = cmd_run_evaluation(args) or rc
     return rc
 
 

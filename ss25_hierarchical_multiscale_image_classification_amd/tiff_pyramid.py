@@ -115,7 +115,9 @@ def _adobe_rgb_marker() -> bytes:
 class TiffPyramid:
     """Tiled TIFF pyramid.  ``level_dimensions`` / ``level_downsamples`` as in openslide."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, samples: Sequence[int] = (3, 4)):
+        """``samples``: the samples per pixel a pyramid level may have -- RGB / RGBA for slides; ``read_mask_level`` also
+        admits 1 (grayscale evaluation masks)."""
         self.path = path
         self._mm = np.memmap(path, dtype=np.uint8, mode="r")
         self._buf = memoryview(self._mm)
@@ -125,7 +127,7 @@ class TiffPyramid:
                 continue
             bits = t.get(258, [8])
             spp = t.get(277, [1])[0]
-            if any(b != 8 for b in bits) or spp not in (3, 4) or t.get(284, [1])[0] != 1:
+            if any(b != 8 for b in bits) or spp not in samples or t.get(284, [1])[0] != 1:
                 continue
             lv = TiffLevel(width=t[256][0], height=t[257][0], tile_w=t[322][0], tile_h=t[323][0],
                            compression=t.get(259, [1])[0], photometric=t.get(262, [2])[0], samples=spp,
@@ -134,7 +136,7 @@ class TiffPyramid:
                 raise TiffError(f"unsupported tile compression {lv.compression} (none, JPEG and deflate are read)")
             levels.append(lv)
         if not levels:
-            raise TiffError("no tiled 8-bit RGB image directory found")
+            raise TiffError(f"no tiled 8-bit image directory with {' or '.join(map(str, samples))} samples per pixel found")
         levels.sort(key=lambda l: -l.width * l.height)
         self.levels: List[TiffLevel] = levels
         self.level_count = len(levels)
@@ -144,7 +146,7 @@ class TiffPyramid:
 
     # ---- tiles -------------------------------------------------------------------------
     def _decode_tile(self, lv: TiffLevel, index: int) -> Optional[np.ndarray]:
-        """uint8[tile_h, tile_w, 3] or None for a missing tile."""
+        """uint8[tile_h, tile_w, 3] (uint8[tile_h, tile_w, 1] for a grayscale level) or None for a missing tile."""
         off, cnt = lv.offsets[index], lv.counts[index]
         if cnt == 0:
             return None
@@ -164,7 +166,7 @@ class TiffPyramid:
                 data = data[:2] + _adobe_rgb_marker() + data[2:]
             im = Image.open(io.BytesIO(data))
             im.load()
-            a = np.asarray(im.convert("RGB"))
+            a = np.asarray(im.convert("L"))[:, :, None] if lv.samples == 1 else np.asarray(im.convert("RGB"))
             if a.shape[0] != lv.tile_h or a.shape[1] != lv.tile_w:
                 raise TiffError("JPEG tile size does not match the directory")
             return a
@@ -312,6 +314,22 @@ class TiffPyramid:
         return out
 
 
+def read_mask_level(path: str, level: int) -> np.ndarray:
+    """uint8[H, W] of level ``level`` of an evaluation mask, channel 0 of openslide's ``read_region((0, 0), level, dims)``
+    (evaluation_FROC.py:29-30): tiled 8-bit grayscale (1 sample, the value itself), RGB or RGBA (the red sample)
+    directories; compression none, deflate or JPEG.  TiffError for LZW and for a file with fewer than ``level + 1``
+    levels."""
+    p = TiffPyramid(path, samples=(1, 3, 4))
+    if level >= p.level_count:
+        raise TiffError(f"{path} has {p.level_count} levels, level {level} was asked for")
+    lv = p.levels[level]
+    out = np.zeros((lv.height, lv.width), np.uint8)
+    for tr in range(lv.tiles_down):
+        band = p.read_band(level, tr)
+        out[tr * lv.tile_h:tr * lv.tile_h + band.shape[0]] = band[:, :, 0]
+    return out
+
+
 def _split_jpeg_tables(data: bytes) -> Tuple[bytes, bytes]:
     """A complete baseline JPEG -> (tables-only stream SOI DQT.. DHT.. EOI, abbreviated image stream without
     DQT / DHT): the two halves of TIFF's JPEGTables (tag 347) scheme, the form CAMELYON16's files use."""
@@ -339,7 +357,7 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                      quality: int = 90, bigtiff: bool = False, missing: Sequence[Tuple[int, int, int]] = (),
                      jpeg_tables: bool = False, subsampling: int = -1, jpeg_options: Optional[dict] = None):
     """Minimal writer of a tiled pyramid (tests and synthetic data only): ``levels`` are uint8[H,W,3]
-    arrays, largest first.  compression: "none" | "deflate" | "jpeg" (YCbCr; every tile a complete JPEG, or with
+    arrays, or uint8[H,W] for single-sample (grayscale, MinIsBlack) directories, largest first.  compression: "none" | "deflate" | "jpeg" (YCbCr; every tile a complete JPEG, or with
     ``jpeg_tables=True`` abbreviated streams plus one JPEGTables tag per directory, as real slide files have
     them).  ``missing``: (level, ty, tx) tiles written with byte count 0."""
     from PIL import Image
@@ -359,7 +377,7 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                 if (li, ty, tx) in missing:
                     offs.append(0), cnts.append(0)
                     continue
-                t = np.zeros((tile, tile, 3), np.uint8)
+                t = np.zeros((tile, tile) if img.ndim == 2 else (tile, tile, 3), np.uint8)
                 part = img[ty * tile:(ty + 1) * tile, tx * tile:(tx + 1) * tile]
                 t[:part.shape[0], :part.shape[1]] = part
                 if comp == 1:
@@ -368,7 +386,7 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                     data = zlib.compress(t.tobytes(), 6)
                 else:
                     bio = io.BytesIO()
-                    Image.fromarray(t, "RGB").save(bio, "JPEG", quality=quality, subsampling=subsampling, **(jpeg_options or {}))
+                    Image.fromarray(t, "L" if img.ndim == 2 else "RGB").save(bio, "JPEG", quality=quality, subsampling=subsampling, **(jpeg_options or {}))
                     data = bio.getvalue()
                     if jpeg_tables:  # fixed quality, default Huffman tables: every tile shares one set
                         tb, data = _split_jpeg_tables(data)
@@ -378,7 +396,7 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                 offs.append(pos), cnts.append(len(data))
                 blobs.append(data)
                 pos += len(data)
-        ifd_specs.append((w, h, ta * td, offs, cnts))
+        ifd_specs.append((w, h, ta * td, offs, cnts, 1 if img.ndim == 2 else 3))
         tables_of_level.append(level_tables)
     out = bytearray()
     # data area first, then IFDs (offsets known up front)
@@ -386,10 +404,10 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
     ifd_pos = (16 if bigtiff else 8) + len(body)
     chunks = []
     cur = ifd_pos
-    for li, (w, h, nt, offs, cnts) in enumerate(ifd_specs):
-        photometric = 6 if comp == 7 else 2
-        entries = [(254, 4, [1 if li else 0]), (256, 4, [w]), (257, 4, [h]), (258, 3, [8, 8, 8]), (259, 3, [comp]),
-                   (262, 3, [photometric]), (277, 3, [3]), (284, 3, [1]), (322, 4, [tile]), (323, 4, [tile]),
+    for li, (w, h, nt, offs, cnts, spp) in enumerate(ifd_specs):
+        photometric = 1 if spp == 1 else 6 if comp == 7 else 2
+        entries = [(254, 4, [1 if li else 0]), (256, 4, [w]), (257, 4, [h]), (258, 3, [8] * spp), (259, 3, [comp]),
+                   (262, 3, [photometric]), (277, 3, [spp]), (284, 3, [1]), (322, 4, [tile]), (323, 4, [tile]),
                    (324, 16 if bigtiff else 4, offs), (325, 16 if bigtiff else 4, cnts)]
         if tables_of_level[li] is not None:
             entries.append((347, 7, list(tables_of_level[li])))  # JPEGTables (UNDEFINED bytes); tags stay sorted
