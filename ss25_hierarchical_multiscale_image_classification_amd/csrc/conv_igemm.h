@@ -2082,23 +2082,31 @@ static int launch_conv_projk(const void* tmp, const ConvW& w2, const ConvW& wp, 
 // parity classes; input position (2y + PY, 2x + PX) only ever meets the taps kh with kh + PY odd ... i.e. kh = 1 for PY = 0 and
 // kh in {0, 2} for PY = 1 (same in x): 1, 2, 2 and 4 taps instead of 9 each -- a quarter of the MFMAs of the 3x3 convolution
 // over the zero-interleaved map.  `g` = gradient wrt the conv output on the coarse HC x HC grid [n][HC][HC][CG]; `wc` = the class's
-// weights [CX][taps][CG] (pack mode 3 of train_amp.hip); `dx` = [n][2 HC][2 HC][CX], this class's positions written.
+// weights [CX][taps][CG] (pack mode 3 of train.hip / train_amp.hip); `dx` = [n][2 HC][2 HC][CX], this class's positions written.
 template <typename T, int CG, int CX, int HC, int TKH, int TKW, int PY, int PX>
 static int launch_dgrad_s2_class(const void* g, const void* wc, const float* zero_bias, void* dx, int n, hipStream_t s,
                                  const char* zero_page) {
-  using C = TileCfg<CX>;
-  constexpr int BM = C::BM, BN = C::BN, NSTAGE = C::NSTAGE;
-  constexpr int THREADS = (BM / 64) * (BN / 64) * 64;
-  constexpr int LDS = NSTAGE * (BM + BN) * 128;
-  auto kern = conv_glds_kernel<T, CG, CX, HC, HC, 1, 1, BM, BN, NSTAGE, false, false, false, false, TKH, TKW, 4 | (PY << 1) | PX>;
-  static bool attr_done[kMaxDevices] = {};
-  if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
   const int M = n * HC * HC;
-  const int n_mtiles = (M + BM - 1) / BM;
-  const int mt8 = (n_mtiles + 7) / 8 * 8;
-  dim3 grid(mt8 * (CX / BN));
-  hipLaunchKernelGGL(kern, grid, dim3(THREADS), LDS, s, (const T*)g, (const T*)wc, zero_bias, (const T*)nullptr, dx, M, n_mtiles,
-                     zero_page, (const T*)nullptr, (const float*)nullptr, (void*)nullptr);
+  if constexpr (sizeof(T) == 4) {
+    // the fp32 training step runs on the v1 kernel (exact f32 MFMA), as launch_conv does
+    constexpr int BN = 64;
+    dim3 grid((M + 127) / 128, CX / BN);
+    hipLaunchKernelGGL((conv_igemm_kernel<T, CG, CX, HC, HC, 1, 1, BN, false, false, false, false, TKH, TKW, 4 | (PY << 1) | PX>), grid,
+                       dim3(256), 0, s, (const T*)g, (const T*)wc, zero_bias, (const T*)nullptr, dx, M);
+  } else {
+    using C = TileCfg<CX>;
+    constexpr int BM = C::BM, BN = C::BN, NSTAGE = C::NSTAGE;
+    constexpr int THREADS = (BM / 64) * (BN / 64) * 64;
+    constexpr int LDS = NSTAGE * (BM + BN) * 128;
+    auto kern = conv_glds_kernel<T, CG, CX, HC, HC, 1, 1, BM, BN, NSTAGE, false, false, false, false, TKH, TKW, 4 | (PY << 1) | PX>;
+    static bool attr_done[kMaxDevices] = {};
+    if (int rc_attr = ensure_dynamic_lds((const void*)kern, LDS, attr_done)) return rc_attr;
+    const int n_mtiles = (M + BM - 1) / BM;
+    const int mt8 = (n_mtiles + 7) / 8 * 8;
+    dim3 grid(mt8 * (CX / BN));
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), LDS, s, (const T*)g, (const T*)wc, zero_bias, (const T*)nullptr, dx, M, n_mtiles,
+                       zero_page, (const T*)nullptr, (const float*)nullptr, (void*)nullptr);
+  }
   return (int)hipGetLastError();
 }
 // all four classes of a 3x3 / stride 2 conv (KS3 = true) or the one class of a 1x1 / stride 2 conv (the other positions of dx
@@ -2112,27 +2120,6 @@ static int launch_dgrad_s2(const void* g, const void* wc, const float* zero_bias
   if (int rc = launch_dgrad_s2_class<T, CG, CX, HC, 1, 2, 0, 1>(g, w + blk, zero_bias, dx, n, s, zero_page)) return rc;
   if (int rc = launch_dgrad_s2_class<T, CG, CX, HC, 2, 1, 1, 0>(g, w + 3 * blk, zero_bias, dx, n, s, zero_page)) return rc;
   return launch_dgrad_s2_class<T, CG, CX, HC, 2, 2, 1, 1>(g, w + 5 * blk, zero_bias, dx, n, s, zero_page);
-}
-
-// the same four classes on the v1 kernel (the fp32 training step: exact f32 MFMA)
-template <typename T, int CG, int CX, int HC, int TKH, int TKW, int PY, int PX>
-static int launch_dgrad_s2_class_v1(const void* g, const void* wc, const float* zero_bias, void* dx, int n, hipStream_t s) {
-  constexpr int BN = 64;
-  const int M = n * HC * HC;
-  dim3 grid((M + 127) / 128, CX / BN);
-  hipLaunchKernelGGL((conv_igemm_kernel<T, CG, CX, HC, HC, 1, 1, BN, false, false, false, false, TKH, TKW, 4 | (PY << 1) | PX>), grid,
-                     dim3(256), 0, s, (const T*)g, (const T*)wc, zero_bias, (const T*)nullptr, dx, M);
-  return (int)hipGetLastError();
-}
-template <typename T, int CG, int CX, int HC, bool KS3>
-static int launch_dgrad_s2_v1(const void* g, const void* wc, const float* zero_bias, void* dx, int n, hipStream_t s) {
-  const T* w = (const T*)wc;
-  constexpr size_t blk = (size_t)CX * CG;
-  if constexpr (!KS3) return launch_dgrad_s2_class_v1<T, CG, CX, HC, 1, 1, 0, 0>(g, w, zero_bias, dx, n, s);
-  if (int rc = launch_dgrad_s2_class_v1<T, CG, CX, HC, 1, 1, 0, 0>(g, w, zero_bias, dx, n, s)) return rc;
-  if (int rc = launch_dgrad_s2_class_v1<T, CG, CX, HC, 1, 2, 0, 1>(g, w + blk, zero_bias, dx, n, s)) return rc;
-  if (int rc = launch_dgrad_s2_class_v1<T, CG, CX, HC, 2, 1, 1, 0>(g, w + 3 * blk, zero_bias, dx, n, s)) return rc;
-  return launch_dgrad_s2_class_v1<T, CG, CX, HC, 2, 2, 1, 1>(g, w + 5 * blk, zero_bias, dx, n, s);
 }
 
 // 3x3 / stride 2 conv (+BN+ReLU) of a down-sampling BasicBlock with its 1x1 / stride 2 projection

@@ -3,43 +3,24 @@
 // autocast, src/models/simclr.py:85-96), convolutions on the exact f32 MFMA (v_mfma_f32_32x32x2_f32).
 //
 //   forward   conv (implicit GEMM, the v1 kernel of conv_igemm.h on re-packed weights) -> batch statistics
-//             (fp64 atomics) -> normalise (+ residual) (+ ReLU); 3x3/2 max-pool with saved arg-max;
-//             global average pool.  Pre-BN and post-activation maps of every conv are kept for the backward.
+//             (fp64 per-workgroup partial sums added in a fixed order, no atomics) -> normalise (+ residual) (+ ReLU);
+//             3x3/2 max-pool with saved arg-max; global average pool.  Pre-BN and post-activation maps of every conv are
+//             kept for the backward.
 //   backward  BN backward (two passes: d gamma / d beta, then dx), conv weight gradient (MFMA GEMM over the
-//             pixel axis, split-K with fp32 atomics), conv data gradient = the forward kernel on flipped /
-//             transposed weights (stride-2 layers: by parity class), max-pool / average-pool
+//             pixel axis, split-K into per-slice partials summed in a fixed order), conv data gradient = the forward
+//             kernel on flipped / transposed weights (stride-2 layers: by parity class), max-pool / average-pool
 //             backward, ReLU masks fused into the consumers.
 //   plus      linear layers (projector, fc) on a strided fp32 MFMA GEMM, weighted cross-entropy, Adam.
+//
+// The host driver of the forward and backward is shared with train_amp.hip (train_common.h); this file supplies the
+// fp32 kernels, the workspace plan and the Fp32Step precision struct.
 //
 // Activations are NHWC fp32.  Parameters live in ONE flat fp32 buffer in a fixed order (per conv: weight in
 // the PyTorch layout [Cout][Cin][kh][kw], then BN gamma, beta); running statistics in a second flat buffer
 // (per conv: running_mean, running_var); gradients in a buffer shaped like the parameters.
-#include "conv_igemm.h"
 #include "train_common.h"
 
 namespace hipac {
-
-// ---------------------------------------------------------------------------------------------
-// workspace of one forward (everything the backward needs) + scratch shared by forward / backward
-// ---------------------------------------------------------------------------------------------
-struct TrainPlan {
-  size_t xin;               // float[B,230,232,4]
-  size_t pre[kNumConvs];    // conv output before BN
-  size_t post[kNumConvs];   // after BN (+ residual) (+ ReLU)
-  size_t pool, pool_idx;    // float[B,56,56,64], uint8 arg-max (0..8, 9 = none)
-  size_t mean_rstd;         // per conv: mean[cout], rstd[cout] (floats), packed by stat_offset
-  size_t sums;              // double[2 * 512] scratch of the statistics / BN-backward reductions
-  size_t red;               // double[kRedBlocks32][2 * 512]: per-workgroup partial sums of one reduction pass (no atomics)
-  size_t wpack;             // packed forward weights of all convs
-  size_t wpack_d;           // packed data-gradient weights (largest conv)
-  size_t wgrad_p;           // packed weight-gradient accumulator (largest conv)
-  size_t zero_bias;         // float[512] zeros
-  size_t g[3];              // gradient maps (largest activation each)
-  size_t up;                // gradient through a 1x1 / stride-2 projection, on the fine grid
-  size_t total;
-};
-
-constexpr int kRedBlocks32 = 512;  // workgroups of a BN reduction pass = rows of the partial-sum table
 
 // split K of conv i's weight gradient over `slices` chunks of `chunk` pixels so that the launch has ~2048 workgroups
 static void wgrad_split(int i, long long M, long long& slices, long long& chunk) {
@@ -52,8 +33,14 @@ static void wgrad_split(int i, long long M, long long& slices, long long& chunk)
   slices = (M + chunk - 1) / chunk;
 }
 
+static size_t wpack_offset(int i) {
+  size_t o = 0;
+  for (int k = 0; k < i; ++k) o += packed_w_floats(k);
+  return o;
+}
+
 static TrainPlan make_train_plan(int B) {
-  TrainPlan p;
+  TrainPlan p{};
   size_t off = 0;
   auto take = [&](size_t bytes) {
     size_t o = off;
@@ -74,10 +61,9 @@ static TrainPlan make_train_plan(int B) {
   p.pool_idx = take(b * 56 * 56 * 64);
   p.mean_rstd = take(stat_offset(kNumConvs) * 4);
   p.sums = take(2 * 512 * 8);
-  p.red = take((size_t)kRedBlocks32 * 1024 * 8);
-  size_t wtot = 0;
-  for (int i = 0; i < kNumConvs; ++i) wtot += packed_w_floats(i);
-  p.wpack = take(wtot * 4);
+  p.red = take((size_t)kRedBlocks * 1024 * 8);
+  const size_t wpack = take(wpack_offset(kNumConvs) * 4);
+  for (int i = 0; i < kNumConvs; ++i) p.wpack[i] = wpack + wpack_offset(i) * 4;
   p.wpack_d = take(maxw * 4);
   size_t maxpart = 0;  // split-K partials of a weight gradient: [slices][packed weights], summed in slice order afterwards
   for (int i = 0; i < kNumConvs; ++i) {
@@ -92,11 +78,6 @@ static TrainPlan make_train_plan(int B) {
   p.up = take(b * 56 * 56 * 128 * 4);  // largest: layer2 entry (128 ch at 56 x 56)
   p.total = off;
   return p;
-}
-static size_t wpack_offset(int i) {
-  size_t o = 0;
-  for (int k = 0; k < i; ++k) o += packed_w_floats(k);
-  return o;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -120,7 +101,7 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ w
   if (mode == 0) dst[(size_t)co * ks * ks * cin + (size_t)(kh * ks + kw) * cin + ci] = v;
   else if (mode == 1) dst[(size_t)ci * ks * ks * cout + (size_t)((ks - 1 - kh) * ks + ks - 1 - kw) * cout + co] = v;
   else if (mode == 3) {
-    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2_v1, conv_igemm.h): class (py, px) = (kh != 1, kw != 1),
+    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2, conv_igemm.h): class (py, px) = (kh != 1, kw != 1),
     // taps (a, b) = ((2 - kh) / 2, (2 - kw) / 2); blocks of 1, 2, 2, 4 taps back to back, each [ci][tap][co]
     const int py = kh != 1, px = kw != 1, a = py ? (2 - kh) / 2 : 0, b = px ? (2 - kw) / 2 : 0;
     const int ntap = (py ? 2 : 1) * (px ? 2 : 1), tap = a * (px ? 2 : 1) + b;
@@ -686,87 +667,42 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // launch helpers
 // ---------------------------------------------------------------------------------------------
 
-// forward-kernel dispatch on the fixed layer geometries (v1 implicit-GEMM kernel, fp32, no epilogue extras)
-template <int CIN, int COUT, int HI, int KS, int STRIDE>
-static int conv_f32(const float* in, const float* wp, const float* zero_bias, float* out, int n, hipStream_t s) {
-  ConvW w{const_cast<float*>(wp), const_cast<float*>(zero_bias)};
-  return launch_conv<float, CIN, COUT, HI, HI, KS, STRIDE, false, false, false>(in, w, nullptr, out, n, s);
-}
-// conv i of the table on input `in`
-static int conv_forward(int i, const float* in, const float* wp, const float* zb, float* out, int n, hipStream_t s) {
-  const ConvDesc& d = kConvs[i];
-  if (i == 0) {
-    ConvW w{const_cast<float*>(wp), const_cast<float*>(zb)};
-    return launch_conv<float, 4, 64, 224, 224, 7, 2, false, false, false, true>(in, w, nullptr, out, n, s);
+// the fp32 precision of the shared driver (train_common.h)
+struct Fp32Step {
+  using T = float;
+  static constexpr const char* kName = "train";
+  static constexpr int kMaxBatch = 4096;  // 32-bit pixel offsets
+  static constexpr int kPrec = HIPAC_PREC_FP32;
+  static constexpr auto pack_w = pack_w_kernel;
+  static TrainPlan plan(int B) { return make_train_plan(B); }
+  static int bn_forward(const TrainCtx& c, int i, int n, const float* resid, int relu);
+  static int bn_backward(const TrainCtx& c, int i, int n, const float* dy, const float* ymask, float* dx, float* grads,
+                         int accumulate);
+  static int conv_wgrad(const TrainCtx& c, int i, int n, const float* X, const float* dY, float* grads, int accumulate);
+  // one thread per channel of an output position (pool) or of an input position (its backward)
+  static void maxpool(const float* in, float* out, unsigned char* idx, int n, hipStream_t s) {
+    const long long total = (long long)n * 56 * 56 * 64;
+    hipLaunchKernelGGL(maxpool_idx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, idx, total);
   }
-  if (d.ks == 3 && d.stride == 1) {
-    switch (d.cout) {
-      case 64: return conv_f32<64, 64, 56, 3, 1>(in, wp, zb, out, n, s);
-      case 128: return conv_f32<128, 128, 28, 3, 1>(in, wp, zb, out, n, s);
-      case 256: return conv_f32<256, 256, 14, 3, 1>(in, wp, zb, out, n, s);
-      default: return conv_f32<512, 512, 7, 3, 1>(in, wp, zb, out, n, s);
-    }
+  static void maxpool_bwd(const float* dout, const unsigned char* idx, float* din, int n, hipStream_t s) {
+    const long long total = (long long)n * 112 * 112 * 64;
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dout, idx, din, total);
   }
-  if (d.ks == 3) {
-    switch (d.cout) {
-      case 128: return conv_f32<64, 128, 56, 3, 2>(in, wp, zb, out, n, s);
-      case 256: return conv_f32<128, 256, 28, 3, 2>(in, wp, zb, out, n, s);
-      default: return conv_f32<256, 512, 14, 3, 2>(in, wp, zb, out, n, s);
-    }
+  static void avgpool(const float* last, float* feats, int n, hipStream_t s) {
+    hipLaunchKernelGGL(avgpool_kernel, dim3(n), dim3(256), 0, s, last, feats, n);
   }
-  switch (d.cout) {
-    case 128: return conv_f32<64, 128, 56, 1, 2>(in, wp, zb, out, n, s);
-    case 256: return conv_f32<128, 256, 28, 1, 2>(in, wp, zb, out, n, s);
-    default: return conv_f32<256, 512, 14, 1, 2>(in, wp, zb, out, n, s);
+  static void avgpool_bwd(const float* dfeats, const float* last, float* dlast, int n, hipStream_t s) {
+    const long long total = (long long)n * 49 * 512;
+    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dfeats, last, dlast, total);
   }
-}
-// data gradient of a 3x3 / stride 1 conv i: g (gradient wrt the conv output) -> gradient wrt the conv input, with weights packed
-// in mode 1 (stride-2 convs: conv_dgrad_s2)
-static int conv_dgrad(int i, const float* g, const float* wd, const float* zb, float* out, int n, hipStream_t s) {
-  switch (kConvs[i].cout) {
-    case 64: return conv_f32<64, 64, 56, 3, 1>(g, wd, zb, out, n, s);
-    case 128: return conv_f32<128, 128, 28, 3, 1>(g, wd, zb, out, n, s);
-    case 256: return conv_f32<256, 256, 14, 3, 1>(g, wd, zb, out, n, s);
-    default: return conv_f32<512, 512, 7, 3, 1>(g, wd, zb, out, n, s);
+  static void add_mask(const float* a, const float* b, const float* y, float* out, long long n_elems, hipStream_t s) {
+    const long long n4 = n_elems / 4;
+    hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n4)), dim3(256), 0, s, a, b, y, out, n4);
   }
-}
-
-// data gradient of a STRIDE-2 conv i by parity classes: g on the coarse grid, weights in mode 3 (3x3) or 1 (1x1; `out` zeroed)
-static int conv_dgrad_s2(int i, const float* g, const float* wd, const float* zb, float* out, int n, hipStream_t s) {
-  const ConvDesc& d = kConvs[i];
-  if (d.ks == 3) {
-    switch (d.cout) {
-      case 128: return launch_dgrad_s2_v1<float, 128, 64, 28, true>(g, wd, zb, out, n, s);
-      case 256: return launch_dgrad_s2_v1<float, 256, 128, 14, true>(g, wd, zb, out, n, s);
-      default: return launch_dgrad_s2_v1<float, 512, 256, 7, true>(g, wd, zb, out, n, s);
-    }
-  }
-  switch (d.cout) {
-    case 128: return launch_dgrad_s2_v1<float, 128, 64, 28, false>(g, wd, zb, out, n, s);
-    case 256: return launch_dgrad_s2_v1<float, 256, 128, 14, false>(g, wd, zb, out, n, s);
-    default: return launch_dgrad_s2_v1<float, 512, 256, 7, false>(g, wd, zb, out, n, s);
-  }
-}
-
-static int pack_weights(const float* w, float* dst, int i, int mode, hipStream_t s) {
-  const ConvDesc& d = kConvs[i];
-  const long long total = (long long)conv_w_floats(i);
-  if (mode == 2) HIPAC_CHECK_HIP(hipMemsetAsync(dst, 0, packed_w_floats(0) * 4, s));
-  hipLaunchKernelGGL(pack_w_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, d.cout, d.cin, d.ks, mode);
-  return (int)hipGetLastError();
-}
-
-struct BnCtx {
-  const float* params;  // flat parameter buffer
-  float* stats;         // running statistics (may be null: not updated)
-  char* ws;
-  const TrainPlan* p;
-  float eps, momentum;
-  hipStream_t s;
 };
 
 // batch-norm (training statistics) of conv i's output, optional residual and ReLU
-static int bn_forward(const BnCtx& c, int i, int n, const float* resid, int relu) {
+int Fp32Step::bn_forward(const TrainCtx& c, int i, int n, const float* resid, int relu) {
   const ConvDesc& d = kConvs[i];
   const long long M = (long long)n * d.hout * d.hout;
   const float* x = (const float*)(c.ws + c.p->pre[i]);
@@ -778,7 +714,7 @@ static int bn_forward(const BnCtx& c, int i, int n, const float* resid, int relu
   double* part = (double*)(c.ws + c.p->red);
   const int rows_per_pass = 256 / (d.cout / 4);
   long long gs = (M + rows_per_pass - 1) / rows_per_pass;
-  if (gs > kRedBlocks32) gs = kRedBlocks32;  // 2 workgroups per CU
+  if (gs > kRedBlocks) gs = kRedBlocks;  // 2 workgroups per CU
   hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)gs), dim3(256), 0, c.s, x, M, d.cout, part);
   hipLaunchKernelGGL(bn_sum_parts32_kernel, dim3((d.cout + 7) / 8), dim3(256), 0, c.s, (const double*)part, (int)gs, d.cout, sums);
   float* rm = c.stats ? c.stats + stat_offset(i) : nullptr;
@@ -791,8 +727,8 @@ static int bn_forward(const BnCtx& c, int i, int n, const float* resid, int relu
 }
 
 // BN backward of conv i: dy (masked by ymask > 0 if given) -> dx (may alias dy), d gamma / d beta into grads
-static int bn_backward(const BnCtx& c, int i, int n, const float* dy, const float* ymask, float* dx, float* grads,
-                       int accumulate) {
+int Fp32Step::bn_backward(const TrainCtx& c, int i, int n, const float* dy, const float* ymask, float* dx, float* grads,
+                          int accumulate) {
   const ConvDesc& d = kConvs[i];
   const long long M = (long long)n * d.hout * d.hout;
   const float* x = (const float*)(c.ws + c.p->pre[i]);
@@ -804,7 +740,7 @@ static int bn_backward(const BnCtx& c, int i, int n, const float* dy, const floa
   double* part = (double*)(c.ws + c.p->red);
   const int rows_per_pass = 256 / (d.cout / 4);
   long long gs = (M + rows_per_pass - 1) / rows_per_pass;
-  if (gs > kRedBlocks32) gs = kRedBlocks32;  // 2 workgroups per CU
+  if (gs > kRedBlocks) gs = kRedBlocks;  // 2 workgroups per CU
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)gs), dim3(256), 0, c.s, dy, x, ymask, M, d.cout, mean, rstd, part);
   hipLaunchKernelGGL(bn_sum_parts32_kernel, dim3((d.cout + 7) / 8), dim3(256), 0, c.s, (const double*)part, (int)gs, d.cout, sums);
   const long long n4 = M * d.cout / 4;
@@ -814,7 +750,7 @@ static int bn_backward(const BnCtx& c, int i, int n, const float* dy, const floa
 }
 
 // weight gradient of conv i: X = the conv's input map, dY = gradient wrt its output -> grads (PyTorch layout)
-static int conv_wgrad(const BnCtx& c, int i, int n, const float* X, const float* dY, float* grads, int accumulate) {
+int Fp32Step::conv_wgrad(const TrainCtx& c, int i, int n, const float* X, const float* dY, float* grads, int accumulate) {
   const ConvDesc& d = kConvs[i];
   float* dwp = (float*)(c.ws + c.p->wgrad_p);
   const long long M = (long long)n * d.hout * d.hout;
@@ -857,168 +793,18 @@ size_t hipac_train_param_floats(void) { return param_offset(kNumConvs); }
 size_t hipac_train_stat_floats(void) { return stat_offset(kNumConvs); }
 size_t hipac_train_workspace_bytes(int batch) { return batch > 0 ? make_train_plan(batch).total : 0; }
 
-// Test tap: byte offset inside the workspace of a map the forward keeps (kind 0: conv output before BN, 1: after BN
-// (+ residual) (+ ReLU), both NHWC float32 [batch][H][W][Cout]; 2: the pooled stem map [batch][56][56][64];
-// 3: batch mean[Cout] then rstd[Cout] of conv `conv`; 4: the pool's arg-max bytes [batch][56][56][64], 0..8 = dy * 3 + dx).
-// Returns -1 on a bad argument.
-int64_t hipac_train_debug_offset(int batch, int kind, int conv) {
-  if (batch <= 0 || conv < 0 || conv >= kNumConvs) return -1;
-  const TrainPlan p = make_train_plan(batch);
-  switch (kind) {
-    case 0: return (int64_t)p.pre[conv];
-    case 1: return (int64_t)p.post[conv];
-    case 2: return (int64_t)p.pool;
-    case 3: return (int64_t)(p.mean_rstd + stat_offset(conv) * 4);
-    case 4: return (int64_t)p.pool_idx;
-    default: return -1;
-  }
-}
+int64_t hipac_train_debug_offset(int batch, int kind, int conv) { return train_debug_offset<Fp32Step>(batch, kind, conv); }
 
 int hipac_train_encoder_forward(const float* params, float* stats, const float* x, int batch, float momentum, float eps,
                                 float* feats, void* workspace, size_t workspace_bytes, void* stream) {
-  HIPAC_REQUIRE(params && x && feats && workspace, HIPAC_EINVAL, "train_forward: null argument");
-  HIPAC_REQUIRE(batch > 0 && batch <= 4096, HIPAC_EINVAL, "train_forward: batch %d (1 .. 4096: 32-bit pixel offsets)", batch);
-  const TrainPlan p = make_train_plan(batch);
-  HIPAC_REQUIRE(workspace_bytes >= p.total, HIPAC_EWORKSPACE, "train_forward: workspace %zu < required %zu", workspace_bytes,
-                p.total);
-  HIPAC_REQUIRE(((uintptr_t)workspace & 255) == 0, HIPAC_EINVAL, "train_forward: workspace must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const int n = batch;
-  float* zb = (float*)(ws + p.zero_bias);
-  HIPAC_CHECK_HIP(hipMemsetAsync(zb, 0, 512 * 4, s));
-  float* wpack = (float*)(ws + p.wpack);
-  for (int i = 0; i < kNumConvs; ++i) {
-    int rc = pack_weights(params + param_offset(i), wpack + wpack_offset(i), i, i == 0 ? 2 : 0, s);
-    HIPAC_REQUIRE(rc == 0, rc, "train_forward: weight pack launch failed (%d)", rc);
-  }
-  int rc = launch_nchw_to_nhwc4(x, ws + p.xin, n, HIPAC_PREC_FP32, s);
-  HIPAC_REQUIRE(rc == 0, rc, "train_forward: input conversion failed (%d)", rc);
-  BnCtx c{params, stats, ws, &p, eps, momentum, s};
-  auto pre = [&](int i) { return (float*)(ws + p.pre[i]); };
-  auto post = [&](int i) { return (float*)(ws + p.post[i]); };
-#define TRY(e)                                                                      \
-  do {                                                                              \
-    int rc__ = (e);                                                                 \
-    HIPAC_REQUIRE(rc__ == 0, rc__, "train: launch failed (%d) at line %d", rc__, __LINE__); \
-  } while (0)
-  // stem
-  TRY(conv_forward(0, (const float*)(ws + p.xin), wpack, zb, pre(0), n, s));
-  TRY(bn_forward(c, 0, n, nullptr, 1));
-  {
-    const long long total = (long long)n * 56 * 56 * 64;
-    hipLaunchKernelGGL(maxpool_idx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)post(0),
-                       (float*)(ws + p.pool), (unsigned char*)(ws + p.pool_idx), total);
-    TRY((int)hipGetLastError());
-  }
-  const float* cur = (const float*)(ws + p.pool);
-  int i = 1;
-  for (int stage = 0; stage < 4; ++stage) {
-    for (int blk = 0; blk < 2; ++blk) {
-      const bool down = stage > 0 && blk == 0;
-      const int c1 = i, c2 = i + 1, ds = down ? i + 2 : -1;
-      TRY(conv_forward(c1, cur, wpack + wpack_offset(c1), zb, pre(c1), n, s));
-      TRY(bn_forward(c, c1, n, nullptr, 1));
-      const float* idt = cur;
-      if (down) {
-        TRY(conv_forward(ds, cur, wpack + wpack_offset(ds), zb, pre(ds), n, s));
-        TRY(bn_forward(c, ds, n, nullptr, 0));
-        idt = post(ds);
-      }
-      TRY(conv_forward(c2, post(c1), wpack + wpack_offset(c2), zb, pre(c2), n, s));
-      TRY(bn_forward(c, c2, n, idt, 1));
-      cur = post(c2);
-      i += down ? 3 : 2;
-    }
-  }
-  hipLaunchKernelGGL(avgpool_kernel, dim3(n), dim3(256), 0, s, cur, feats, n);
-  TRY((int)hipGetLastError());
-  return 0;
+  return train_encoder_forward<Fp32Step>(params, stats, x, batch, momentum, eps, feats, workspace, workspace_bytes,
+                                         (hipStream_t)stream);
 }
 
 int hipac_train_encoder_backward(const float* params, const float* dfeats, int batch, float* grads, int accumulate,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-  HIPAC_REQUIRE(params && dfeats && grads && workspace, HIPAC_EINVAL, "train_backward: null argument");
-  HIPAC_REQUIRE(batch > 0 && batch <= 4096, HIPAC_EINVAL, "train_backward: batch %d", batch);
-  const TrainPlan p = make_train_plan(batch);
-  HIPAC_REQUIRE(workspace_bytes >= p.total, HIPAC_EWORKSPACE, "train_backward: workspace %zu < required %zu", workspace_bytes,
-                p.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const int n = batch;
-  const float* zb = (const float*)(ws + p.zero_bias);
-  float* wd = (float*)(ws + p.wpack_d);
-  BnCtx c{params, nullptr, ws, &p, 0.f, 0.f, s};
-  auto post = [&](int i) { return (float*)(ws + p.post[i]); };
-  float* gA = (float*)(ws + p.g[0]);  // gradient wrt the current block's output (after its ReLU mask)
-  float* gB = (float*)(ws + p.g[1]);
-  float* gC = (float*)(ws + p.g[2]);
-  float* up = (float*)(ws + p.up);
-  // global average pool + the last block's ReLU
-  {
-    const long long total = (long long)n * 49 * 512;
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dfeats, (const float*)post(19),
-                       gA, total);
-    TRY((int)hipGetLastError());
-  }
-  // blocks in reverse.  conv indices of block (stage, blk): see kConvs
-  static const int kFirst[4][2] = {{1, 3}, {5, 8}, {10, 13}, {15, 18}};
-  for (int stage = 3; stage >= 0; --stage) {
-    for (int blk = 1; blk >= 0; --blk) {
-      const bool down = stage > 0 && blk == 0;
-      const int c1 = kFirst[stage][blk], c2 = c1 + 1, ds = down ? c1 + 2 : -1;
-      // input of the block = output of the previous block (the pooled map for the very first); that map is
-      // also the ReLU mask of the gradient handed to the previous block (nothing to mask after the pool)
-      const float* xin_blk;
-      const float* prev_post;
-      if (stage == 0 && blk == 0) xin_blk = (const float*)(ws + p.pool), prev_post = nullptr;
-      else {
-        const int pc2 = (blk == 1 ? kFirst[stage][0] : kFirst[stage - 1][1]) + 1;  // conv2 of the previous block
-        xin_blk = post(pc2), prev_post = xin_blk;
-      }
-      const ConvDesc& d1 = kConvs[c1];
-      const long long n_in4 = (long long)n * d1.hin * d1.hin * d1.cin / 4;
-      // --- main path: bn2 -> conv2 -> (ReLU) bn1 -> conv1
-      TRY(bn_backward(c, c2, n, gA, nullptr, gB, grads, accumulate));                 // gB = d pre(c2)
-      TRY(conv_wgrad(c, c2, n, post(c1), gB, grads, accumulate));
-      TRY(pack_weights(params + param_offset(c2), wd, c2, 1, s));
-      TRY(conv_dgrad(c2, gB, wd, zb, gC, n, s));                                       // gC = d post(c1) (before its ReLU mask)
-      TRY(bn_backward(c, c1, n, gC, post(c1), gC, grads, accumulate));                 // gC = d pre(c1)
-      TRY(conv_wgrad(c, c1, n, xin_blk, gC, grads, accumulate));
-      if (d1.stride == 2) {
-        TRY(pack_weights(params + param_offset(c1), wd, c1, 3, s));
-        TRY(conv_dgrad_s2(c1, gC, wd, zb, gB, n, s));                                  // gB = d block input via the main path
-      } else {
-        TRY(pack_weights(params + param_offset(c1), wd, c1, 1, s));
-        TRY(conv_dgrad(c1, gC, wd, zb, gB, n, s));                                     // gB = d block input via the main path
-      }
-      // --- identity path
-      if (down) {
-        TRY(bn_backward(c, ds, n, gA, nullptr, gC, grads, accumulate));                // gC = d pre(ds)
-        TRY(conv_wgrad(c, ds, n, xin_blk, gC, grads, accumulate));
-        TRY(pack_weights(params + param_offset(ds), wd, ds, 1, s));
-        // 1x1 / stride 2: only the even positions of the fine grid receive a gradient; `up` takes it (gC holds the input)
-        HIPAC_CHECK_HIP(hipMemsetAsync(up, 0, (size_t)n * d1.hin * d1.hin * kConvs[ds].cin * 4, s));
-        TRY(conv_dgrad_s2(ds, gC, wd, zb, up, n, s));
-        hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n_in4)), dim3(256), 0, s, (const float*)gB, (const float*)up, prev_post,
-                           gA, n_in4);
-      } else {
-        hipLaunchKernelGGL(add_mask_kernel, dim3(grid_for(n_in4)), dim3(256), 0, s, (const float*)gB, (const float*)gA, prev_post,
-                           gA, n_in4);
-      }
-      TRY((int)hipGetLastError());
-    }
-  }
-  // max-pool, stem BN (+ ReLU mask), stem weight gradient
-  {
-    const long long total = (long long)n * 112 * 112 * 64;
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)gA,
-                       (const unsigned char*)(ws + p.pool_idx), gB, total);
-    TRY((int)hipGetLastError());
-  }
-  TRY(bn_backward(c, 0, n, gB, post(0), gB, grads, accumulate));
-  TRY(conv_wgrad(c, 0, n, (const float*)(ws + p.xin), gB, grads, accumulate));
-  return 0;
+  return train_encoder_backward<Fp32Step>(params, dfeats, batch, grads, accumulate, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
 }
 
 }  // extern "C"

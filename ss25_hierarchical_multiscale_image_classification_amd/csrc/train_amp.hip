@@ -13,10 +13,9 @@
 //             below: an MFMA GEMM over the pixel axis whose operands (dY and X, both [pixel][channel] in memory) are
 //             read TRANSPOSED from LDS by ds_read_b64_tr_b16, split-K partials in fp32 summed in a fixed order (no
 //             atomics: a step run twice gives the same bits).
-// The gradients that arrive (dfeats) and leave (grads) carry the caller's loss scale.
-#include <stdlib.h>
-
-#include "conv_igemm.h"
+// The gradients that arrive (dfeats) and leave (grads) carry the caller's loss scale.  The host driver of the forward
+// and backward is shared with train.hip (train_common.h); this file supplies the fp16 kernels, the workspace plan and the
+// Fp16Step precision struct.
 #include "train_common.h"
 
 namespace hipac {
@@ -24,32 +23,15 @@ namespace hipac {
 typedef _Float16 h16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-static size_t packed_w_halfs(int i) { return i == 0 ? (size_t)64 * 224 : conv_w_floats(i); }
 static size_t wpack_offset_h(int i) {
   size_t o = 0;
-  for (int k = 0; k < i; ++k) o += (packed_w_halfs(k) + 127) & ~(size_t)127;  // 256-byte aligned rows of the table
+  for (int k = 0; k < i; ++k) o += (packed_w_floats(k) + 127) & ~(size_t)127;  // 256-byte aligned rows of the table
   return o;
 }
-constexpr int kRedBlocks = 512;  // workgroups of a BN reduction pass = rows of the partial-sum table
-
-struct AmpPlan {
-  size_t xin;               // h16[B,230,232,4]
-  size_t pre[kNumConvs];    // conv output before BN, h16
-  size_t post[kNumConvs];   // after BN (+ residual) (+ ReLU), h16
-  size_t pool, pool_idx;    // h16[B,56,56,64], uint8 arg-max
-  size_t mean_rstd;         // floats, packed by stat_offset
-  size_t red;               // double[kRedBlocks][2 * 512] partial sums of one reduction pass
-  size_t sums;              // double[2 * 512]
-  size_t wpack, wpack_d;    // h16 packed forward weights (all convs) / data-gradient weights (largest conv)
-  size_t wg_part;           // float split-K partials of one weight gradient
-  size_t zero_bias, zero_page;
-  size_t g[3], up;          // h16 gradient maps, gradient through a 1x1 / stride-2 projection on the fine grid
-  size_t total;
-};
 constexpr size_t kWgPartBytes = (size_t)160 << 20;
 
-static AmpPlan make_amp_plan(int B) {
-  AmpPlan p;
+static TrainPlan make_amp_plan(int B) {
+  TrainPlan p{};
   size_t off = 0;
   auto take = [&](size_t bytes) {
     size_t o = off;
@@ -64,16 +46,17 @@ static AmpPlan make_amp_plan(int B) {
     p.pre[i] = take(n * 2);
     p.post[i] = take(n * 2);
     if (n > maxact) maxact = n;
-    if (packed_w_halfs(i) > maxw) maxw = packed_w_halfs(i);
+    if (packed_w_floats(i) > maxw) maxw = packed_w_floats(i);
   }
   p.pool = take(b * 56 * 56 * 64 * 2);
   p.pool_idx = take(b * 56 * 56 * 64);
   p.mean_rstd = take(stat_offset(kNumConvs) * 4);
   p.red = take((size_t)kRedBlocks * 1024 * 8);
   p.sums = take(1024 * 8);
-  p.wpack = take(wpack_offset_h(kNumConvs) * 2);
+  const size_t wpack = take(wpack_offset_h(kNumConvs) * 2);
+  for (int i = 0; i < kNumConvs; ++i) p.wpack[i] = wpack + wpack_offset_h(i) * 2;
   p.wpack_d = take(maxw * 2);
-  p.wg_part = take(kWgPartBytes);
+  p.wgrad_p = take(kWgPartBytes);
   p.zero_bias = take(512 * 4);
   p.zero_page = take(256);
   for (int k = 0; k < 3; ++k) p.g[k] = take(maxact * 2);
@@ -629,80 +612,37 @@ __global__ __launch_bounds__(256) void unscale_check_kernel(float* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------------------
-template <int CIN, int COUT, int HI, int KS, int STRIDE>
-static int conv_h(const h16* in, const h16* wp, const float* zero_bias, h16* out, int n, hipStream_t s, const char* zero_page) {
-  ConvW w{const_cast<h16*>(wp), const_cast<float*>(zero_bias)};
-  return launch_conv<h16, CIN, COUT, HI, HI, KS, STRIDE, false, false, false>(in, w, nullptr, out, n, s, zero_page);
-}
-static int conv_forward_h(int i, const h16* in, const h16* wp, const float* zb, h16* out, int n, hipStream_t s, const char* zp) {
-  const ConvDesc& d = kConvs[i];
-  if (i == 0) {
-    ConvW w{const_cast<h16*>(wp), const_cast<float*>(zb)};
-    return launch_conv<h16, 4, 64, 224, 224, 7, 2, false, false, false, true>(in, w, nullptr, out, n, s);
+// the fp16 precision of the shared driver (train_common.h)
+struct Fp16Step {
+  using T = h16;
+  static constexpr const char* kName = "train_amp";
+  static constexpr int kMaxBatch = 2048;  // 32-bit byte offsets
+  static constexpr int kPrec = HIPAC_PREC_FP16;
+  static constexpr auto pack_w = pack_w_h_kernel;
+  static TrainPlan plan(int B) { return make_amp_plan(B); }
+  static int bn_forward(const TrainCtx& c, int i, int n, const h16* resid, int relu);
+  static int bn_backward(const TrainCtx& c, int i, int n, const h16* dy, const h16* ymask, h16* dx, float* grads, int accumulate);
+  static int conv_wgrad(const TrainCtx& c, int i, int n, const h16* X, const h16* dY, float* grads, int accumulate);
+  // 8 channels per thread; the pool's backward: a 2 x 2 quad of input positions x 8 channels per thread
+  static void maxpool(const h16* in, h16* out, unsigned char* idx, int n, hipStream_t s) {
+    const long long total = (long long)n * 56 * 56 * 8;
+    hipLaunchKernelGGL(maxpool_idx_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, idx, total);
   }
-  if (d.ks == 3 && d.stride == 1) {
-    switch (d.cout) {
-      case 64: return conv_h<64, 64, 56, 3, 1>(in, wp, zb, out, n, s, zp);
-      case 128: return conv_h<128, 128, 28, 3, 1>(in, wp, zb, out, n, s, zp);
-      case 256: return conv_h<256, 256, 14, 3, 1>(in, wp, zb, out, n, s, zp);
-      default: return conv_h<512, 512, 7, 3, 1>(in, wp, zb, out, n, s, zp);
-    }
+  static void maxpool_bwd(const h16* dout, const unsigned char* idx, h16* din, int n, hipStream_t s) {
+    const long long total = (long long)n * 56 * 56 * 8;
+    hipLaunchKernelGGL(maxpool_bwd_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dout, idx, din, total);
   }
-  if (d.ks == 3) {
-    switch (d.cout) {
-      case 128: return conv_h<64, 128, 56, 3, 2>(in, wp, zb, out, n, s, zp);
-      case 256: return conv_h<128, 256, 28, 3, 2>(in, wp, zb, out, n, s, zp);
-      default: return conv_h<256, 512, 14, 3, 2>(in, wp, zb, out, n, s, zp);
-    }
+  static void avgpool(const h16* last, float* feats, int n, hipStream_t s) {
+    hipLaunchKernelGGL(avgpool_h_kernel, dim3(n), dim3(256), 0, s, last, feats, n);
   }
-  switch (d.cout) {
-    case 128: return conv_h<64, 128, 56, 1, 2>(in, wp, zb, out, n, s, zp);
-    case 256: return conv_h<128, 256, 28, 1, 2>(in, wp, zb, out, n, s, zp);
-    default: return conv_h<256, 512, 14, 1, 2>(in, wp, zb, out, n, s, zp);
+  static void avgpool_bwd(const float* dfeats, const h16* last, h16* dlast, int n, hipStream_t s) {
+    const long long total = (long long)n * 49 * 512;
+    hipLaunchKernelGGL(avgpool_bwd_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dfeats, last, dlast, total);
   }
-}
-// data gradient of a STRIDE-2 conv i by parity classes: g = gradient wrt the conv output on the coarse grid, weights in mode 3
-// (3x3) or mode 1 (1x1; `out` zeroed by the caller)
-static int conv_dgrad_s2_h(int i, const h16* g, const h16* wd, const float* zb, h16* out, int n, hipStream_t s, const char* zp) {
-  const ConvDesc& d = kConvs[i];
-  if (d.ks == 3) {
-    switch (d.cout) {
-      case 128: return launch_dgrad_s2<h16, 128, 64, 28, true>(g, wd, zb, out, n, s, zp);
-      case 256: return launch_dgrad_s2<h16, 256, 128, 14, true>(g, wd, zb, out, n, s, zp);
-      default: return launch_dgrad_s2<h16, 512, 256, 7, true>(g, wd, zb, out, n, s, zp);
-    }
+  static void add_mask(const h16* a, const h16* b, const h16* y, h16* out, long long n_elems, hipStream_t s) {
+    const long long n8 = n_elems / 8;
+    hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n8)), dim3(256), 0, s, a, b, y, out, n8);
   }
-  switch (d.cout) {
-    case 128: return launch_dgrad_s2<h16, 128, 64, 28, false>(g, wd, zb, out, n, s, zp);
-    case 256: return launch_dgrad_s2<h16, 256, 128, 14, false>(g, wd, zb, out, n, s, zp);
-    default: return launch_dgrad_s2<h16, 512, 256, 7, false>(g, wd, zb, out, n, s, zp);
-  }
-}
-// data gradient of a 3x3 / stride 1 conv i: g = gradient wrt the conv output, weights in mode 1 (stride-2 convs: conv_dgrad_s2_h)
-static int conv_dgrad_h(int i, const h16* g, const h16* wd, const float* zb, h16* out, int n, hipStream_t s, const char* zp) {
-  switch (kConvs[i].cout) {
-    case 64: return conv_h<64, 64, 56, 3, 1>(g, wd, zb, out, n, s, zp);
-    case 128: return conv_h<128, 128, 28, 3, 1>(g, wd, zb, out, n, s, zp);
-    case 256: return conv_h<256, 256, 14, 3, 1>(g, wd, zb, out, n, s, zp);
-    default: return conv_h<512, 512, 7, 3, 1>(g, wd, zb, out, n, s, zp);
-  }
-}
-
-static int pack_weights_h(const float* w, h16* dst, int i, int mode, hipStream_t s) {
-  const ConvDesc& d = kConvs[i];
-  const long long total = (long long)conv_w_floats(i);
-  if (mode == 2) HIPAC_CHECK_HIP(hipMemsetAsync(dst, 0, packed_w_halfs(0) * 2, s));
-  hipLaunchKernelGGL(pack_w_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, d.cout, d.cin, d.ks, mode);
-  return (int)hipGetLastError();
-}
-
-struct AmpCtx {
-  const float* params;
-  float* stats;
-  char* ws;
-  const AmpPlan* p;
-  float eps, momentum;
-  hipStream_t s;
 };
 
 static int red_blocks(long long M, int C) {
@@ -711,7 +651,7 @@ static int red_blocks(long long M, int C) {
   return (int)(gs > kRedBlocks ? kRedBlocks : gs);
 }
 
-static int bn_forward_h(const AmpCtx& c, int i, int n, const h16* resid, int relu) {
+int Fp16Step::bn_forward(const TrainCtx& c, int i, int n, const h16* resid, int relu) {
   const ConvDesc& d = kConvs[i];
   const long long M = (long long)n * d.hout * d.hout;
   const h16* x = (const h16*)(c.ws + c.p->pre[i]);
@@ -733,7 +673,8 @@ static int bn_forward_h(const AmpCtx& c, int i, int n, const h16* resid, int rel
   return (int)hipGetLastError();
 }
 
-static int bn_backward_h(const AmpCtx& c, int i, int n, const h16* dy, const h16* ymask, h16* dx, float* grads, int accumulate) {
+int Fp16Step::bn_backward(const TrainCtx& c, int i, int n, const h16* dy, const h16* ymask, h16* dx, float* grads,
+                          int accumulate) {
   const ConvDesc& d = kConvs[i];
   const long long M = (long long)n * d.hout * d.hout;
   const h16* x = (const h16*)(c.ws + c.p->pre[i]);
@@ -754,21 +695,20 @@ static int bn_backward_h(const AmpCtx& c, int i, int n, const h16* dy, const h16
 }
 
 // weight gradient of conv i: X = the conv's input map, dY = gradient wrt its output -> grads (PyTorch layout)
-static int conv_wgrad_h(const AmpCtx& c, int i, int n, const h16* X, const h16* dY, float* grads, int accumulate) {
+int Fp16Step::conv_wgrad(const TrainCtx& c, int i, int n, const h16* X, const h16* dY, float* grads, int accumulate) {
   const ConvDesc& d = kConvs[i];
-  float* part = (float*)(c.ws + c.p->wg_part);
+  float* part = (float*)(c.ws + c.p->wgrad_p);
   const long long M = (long long)n * d.hout * d.hout;
   const bool stem = i == 0;
   const size_t pf = stem ? (size_t)7 * 64 * 32 : conv_w_floats(i);
   const bool big = !stem && d.cout >= 128 && d.cin >= 128;
   const int TC = big ? 128 : 64;
-  static const int knob_big = getenv("HIPAC_WG_NTAP_BIG") ? atoi(getenv("HIPAC_WG_NTAP_BIG")) : 1;      // developer knobs; measured (2 x 1024 views, img/s):
-  static const int knob_small = getenv("HIPAC_WG_NTAP_SMALL") ? atoi(getenv("HIPAC_WG_NTAP_SMALL")) : 3;  // (big, small) = (1, 3) 27.9 k, (1, 9) 27.4 k, (3, 3) 26.2 k, (3, 9) 25.8 k, (1, 1) 26.6 k
-  static const int knob_wgs = getenv("HIPAC_WG_TARGET") ? atoi(getenv("HIPAC_WG_TARGET")) : 768;  // workgroups per launch: 256 23.0 k, 512 27.4 k, 768 28.5 k, 1536 27.9 k, 3072 27.1 k
-  const int ntap_wg = stem ? 7 : (d.ks == 1 ? 1 : (big ? knob_big : knob_small));  // taps per workgroup (they share the dY tile)
+  // taps per workgroup (they share the dY tile): the stem's 7 filter rows; 1 for the 128-channel tiles, 3 (one filter row)
+  // for the 64-channel ones -- see DESIGN.md, "Removed alternatives"
+  const int ntap_wg = stem ? 7 : (d.ks == 1 || big ? 1 : 3);
   const int tiles = stem ? 1 : (d.ks * d.ks / ntap_wg) * (d.cout / TC) * (d.cin / TC);
   // split the pixel axis so that the launch has ~768 workgroups (3 per CU); slices bounded by the partials buffer
-  long long slices = (knob_wgs + tiles - 1) / tiles;
+  long long slices = (768 + tiles - 1) / tiles;
   const long long cap = (long long)(kWgPartBytes / (pf * 4));
   if (slices > cap) slices = cap;
   if (slices < 1) slices = 1;
@@ -781,9 +721,7 @@ static int conv_wgrad_h(const AmpCtx& c, int i, int n, const h16* X, const h16* 
   hipLaunchKernelGGL((wgrad_f16_kernel<TC_, NT_, ST_>), grid, dim3(256), 0, c.s, dY, X, part, d.cout, d.cin, d.ks, d.stride, \
                      d.hout, d.hin, M, (int)chunk)
   if (stem) HIPAC_WG(64, 7, true);
-  else if (big && ntap_wg == 3) HIPAC_WG(128, 3, false);
   else if (big) HIPAC_WG(128, 1, false);
-  else if (ntap_wg == 9) HIPAC_WG(64, 9, false);
   else if (ntap_wg == 3) HIPAC_WG(64, 3, false);
   else HIPAC_WG(64, 1, false);
 #undef HIPAC_WG
@@ -802,155 +740,18 @@ extern "C" {
 size_t hipac_train_amp_workspace_bytes(int batch) { return batch > 0 ? make_amp_plan(batch).total : 0; }
 
 // Test tap, as hipac_train_debug_offset but for the fp16 workspace (maps are fp16 NHWC)
-int64_t hipac_train_amp_debug_offset(int batch, int kind, int conv) {
-  if (batch <= 0 || conv < 0 || conv >= kNumConvs) return -1;
-  const AmpPlan p = make_amp_plan(batch);
-  switch (kind) {
-    case 0: return (int64_t)p.pre[conv];
-    case 1: return (int64_t)p.post[conv];
-    case 2: return (int64_t)p.pool;
-    case 3: return (int64_t)(p.mean_rstd + stat_offset(conv) * 4);
-    case 4: return (int64_t)p.pool_idx;
-    default: return -1;
-  }
-}
-
-#define TRY(e)                                                                          \
-  do {                                                                                  \
-    int rc__ = (e);                                                                     \
-    HIPAC_REQUIRE(rc__ == 0, rc__, "train_amp: launch failed (%d) at line %d", rc__, __LINE__); \
-  } while (0)
+int64_t hipac_train_amp_debug_offset(int batch, int kind, int conv) { return train_debug_offset<Fp16Step>(batch, kind, conv); }
 
 int hipac_train_amp_encoder_forward(const float* params, float* stats, const float* x, int batch, float momentum, float eps,
                                     float* feats, void* workspace, size_t workspace_bytes, void* stream) {
-  HIPAC_REQUIRE(params && x && feats && workspace, HIPAC_EINVAL, "train_amp_forward: null argument");
-  HIPAC_REQUIRE(batch > 0 && batch <= 2048, HIPAC_EINVAL, "train_amp_forward: batch %d (1 .. 2048: 32-bit byte offsets)", batch);
-  const AmpPlan p = make_amp_plan(batch);
-  HIPAC_REQUIRE(workspace_bytes >= p.total, HIPAC_EWORKSPACE, "train_amp_forward: workspace %zu < required %zu", workspace_bytes,
-                p.total);
-  HIPAC_REQUIRE(((uintptr_t)workspace & 255) == 0, HIPAC_EINVAL, "train_amp_forward: workspace must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const int n = batch;
-  float* zb = (float*)(ws + p.zero_bias);
-  const char* zp = ws + p.zero_page;
-  HIPAC_CHECK_HIP(hipMemsetAsync(zb, 0, 512 * 4 + 256, s));  // zero_bias and zero_page are adjacent
-  h16* wpack = (h16*)(ws + p.wpack);
-  for (int i = 0; i < kNumConvs; ++i) TRY(pack_weights_h(params + param_offset(i), wpack + wpack_offset_h(i), i, i == 0 ? 2 : 0, s));
-  TRY(launch_nchw_to_nhwc4(x, ws + p.xin, n, HIPAC_PREC_FP16, s));
-  AmpCtx c{params, stats, ws, &p, eps, momentum, s};
-  auto pre = [&](int i) { return (h16*)(ws + p.pre[i]); };
-  auto post = [&](int i) { return (h16*)(ws + p.post[i]); };
-  TRY(conv_forward_h(0, (const h16*)(ws + p.xin), wpack, zb, pre(0), n, s, zp));
-  TRY(bn_forward_h(c, 0, n, nullptr, 1));
-  {
-    const long long total = (long long)n * 56 * 56 * 8;  // 8 channels per thread
-    hipLaunchKernelGGL(maxpool_idx_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const h16*)post(0),
-                       (h16*)(ws + p.pool), (unsigned char*)(ws + p.pool_idx), total);
-    TRY((int)hipGetLastError());
-  }
-  const h16* cur = (const h16*)(ws + p.pool);
-  int i = 1;
-  for (int stage = 0; stage < 4; ++stage) {
-    for (int blk = 0; blk < 2; ++blk) {
-      const bool down = stage > 0 && blk == 0;
-      const int c1 = i, c2 = i + 1, ds = down ? i + 2 : -1;
-      TRY(conv_forward_h(c1, cur, wpack + wpack_offset_h(c1), zb, pre(c1), n, s, zp));
-      TRY(bn_forward_h(c, c1, n, nullptr, 1));
-      const h16* idt = cur;
-      if (down) {
-        TRY(conv_forward_h(ds, cur, wpack + wpack_offset_h(ds), zb, pre(ds), n, s, zp));
-        TRY(bn_forward_h(c, ds, n, nullptr, 0));
-        idt = post(ds);
-      }
-      TRY(conv_forward_h(c2, post(c1), wpack + wpack_offset_h(c2), zb, pre(c2), n, s, zp));
-      TRY(bn_forward_h(c, c2, n, idt, 1));
-      cur = post(c2);
-      i += down ? 3 : 2;
-    }
-  }
-  hipLaunchKernelGGL(avgpool_h_kernel, dim3(n), dim3(256), 0, s, cur, feats, n);
-  TRY((int)hipGetLastError());
-  return 0;
+  return train_encoder_forward<Fp16Step>(params, stats, x, batch, momentum, eps, feats, workspace, workspace_bytes,
+                                         (hipStream_t)stream);
 }
 
 int hipac_train_amp_encoder_backward(const float* params, const float* dfeats, int batch, float* grads, int accumulate,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  HIPAC_REQUIRE(params && dfeats && grads && workspace, HIPAC_EINVAL, "train_amp_backward: null argument");
-  HIPAC_REQUIRE(batch > 0 && batch <= 2048, HIPAC_EINVAL, "train_amp_backward: batch %d", batch);
-  const AmpPlan p = make_amp_plan(batch);
-  HIPAC_REQUIRE(workspace_bytes >= p.total, HIPAC_EWORKSPACE, "train_amp_backward: workspace %zu < required %zu", workspace_bytes,
-                p.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const int n = batch;
-  const float* zb = (const float*)(ws + p.zero_bias);
-  const char* zp = ws + p.zero_page;
-  h16* wd = (h16*)(ws + p.wpack_d);
-  AmpCtx c{params, nullptr, ws, &p, 0.f, 0.f, s};
-  auto post = [&](int i) { return (h16*)(ws + p.post[i]); };
-  h16* gA = (h16*)(ws + p.g[0]);
-  h16* gB = (h16*)(ws + p.g[1]);
-  h16* gC = (h16*)(ws + p.g[2]);
-  h16* up = (h16*)(ws + p.up);
-  {
-    const long long total = (long long)n * 49 * 512;
-    hipLaunchKernelGGL(avgpool_bwd_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dfeats, (const h16*)post(19), gA,
-                       total);
-    TRY((int)hipGetLastError());
-  }
-  static const int kFirst[4][2] = {{1, 3}, {5, 8}, {10, 13}, {15, 18}};
-  for (int stage = 3; stage >= 0; --stage) {
-    for (int blk = 1; blk >= 0; --blk) {
-      const bool down = stage > 0 && blk == 0;
-      const int c1 = kFirst[stage][blk], c2 = c1 + 1, ds = down ? c1 + 2 : -1;
-      const h16* xin_blk;
-      const h16* prev_post;
-      if (stage == 0 && blk == 0) xin_blk = (const h16*)(ws + p.pool), prev_post = nullptr;
-      else {
-        const int pc2 = (blk == 1 ? kFirst[stage][0] : kFirst[stage - 1][1]) + 1;
-        xin_blk = post(pc2), prev_post = xin_blk;
-      }
-      const ConvDesc& d1 = kConvs[c1];
-      const long long n_in8 = (long long)n * d1.hin * d1.hin * d1.cin / 8;
-      TRY(bn_backward_h(c, c2, n, gA, nullptr, gB, grads, accumulate));
-      TRY(conv_wgrad_h(c, c2, n, post(c1), gB, grads, accumulate));
-      TRY(pack_weights_h(params + param_offset(c2), wd, c2, 1, s));
-      TRY(conv_dgrad_h(c2, gB, wd, zb, gC, n, s, zp));
-      TRY(bn_backward_h(c, c1, n, gC, post(c1), gC, grads, accumulate));
-      TRY(conv_wgrad_h(c, c1, n, xin_blk, gC, grads, accumulate));
-      if (d1.stride == 2) {
-        TRY(pack_weights_h(params + param_offset(c1), wd, c1, 3, s));
-        TRY(conv_dgrad_s2_h(c1, gC, wd, zb, gB, n, s, zp));
-      } else {
-        TRY(pack_weights_h(params + param_offset(c1), wd, c1, 1, s));
-        TRY(conv_dgrad_h(c1, gC, wd, zb, gB, n, s, zp));
-      }
-      if (down) {
-        TRY(bn_backward_h(c, ds, n, gA, nullptr, gC, grads, accumulate));
-        TRY(conv_wgrad_h(c, ds, n, xin_blk, gC, grads, accumulate));
-        TRY(pack_weights_h(params + param_offset(ds), wd, ds, 1, s));
-        // 1x1 / stride 2: only the even positions of the fine grid receive a gradient; `up` takes it (gC holds the input)
-        HIPAC_CHECK_HIP(hipMemsetAsync(up, 0, (size_t)n * d1.hin * d1.hin * kConvs[ds].cin * 2, s));
-        TRY(conv_dgrad_s2_h(ds, gC, wd, zb, up, n, s, zp));
-        hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n_in8)), dim3(256), 0, s, (const h16*)gB, (const h16*)up, prev_post, gA,
-                           n_in8);
-      } else {
-        hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n_in8)), dim3(256), 0, s, (const h16*)gB, (const h16*)gA, prev_post, gA,
-                           n_in8);
-      }
-      TRY((int)hipGetLastError());
-    }
-  }
-  {
-    const long long total = (long long)n * 56 * 56 * 8;  // a 2 x 2 quad of positions x 8 channels per thread
-    hipLaunchKernelGGL(maxpool_bwd_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const h16*)gA,
-                       (const unsigned char*)(ws + p.pool_idx), gB, total);
-    TRY((int)hipGetLastError());
-  }
-  TRY(bn_backward_h(c, 0, n, gB, post(0), gB, grads, accumulate));
-  TRY(conv_wgrad_h(c, 0, n, (const h16*)(ws + p.xin), gB, grads, accumulate));
-  return 0;
+  return train_encoder_backward<Fp16Step>(params, dfeats, batch, grads, accumulate, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
 }
 
 // GradScaler.unscale_: grads *= inv_scale in place; found_inf[0] (device int32, zeroed by the caller) is set when a

@@ -36,6 +36,10 @@ DRIVER = textwrap.dedent("""
         for prec in (0, 1, 2):
             assert lib.hipac_resnet18_workspace_bytes(batch, prec) > 0
     assert lib.hipac_train_debug_offset(4, 1, 19) > 0 and lib.hipac_train_debug_offset(4, 9, 0) == -1
+    for batch in (1, 7, 512, 2048):
+        assert lib.hipac_train_amp_workspace_bytes(batch) > 0
+    assert lib.hipac_train_amp_debug_offset(4, 1, 19) > 0 and lib.hipac_train_amp_debug_offset(4, 9, 0) == -1
+    assert lib.hipac_train_amp_debug_offset(4, 0, 20) == -1 and lib.hipac_train_amp_debug_offset(0, 0, 0) == -1
     hb, db, cb = C.c_size_t(), C.c_size_t(), C.c_size_t()
     for W, H in ((5000, 4000), (225, 224), (100000, 100000)):
         for P in (448, 896, 1792):
@@ -46,6 +50,8 @@ DRIVER = textwrap.dedent("""
     # null / out-of-range arguments are answered with error codes before anything touches a device
     assert lib.hipac_resnet18_forward(None, None, 4, 0, None, None, None, None, 0, None) != 0
     assert lib.hipac_train_encoder_forward(None, None, None, 4, 0.1, 1e-5, None, None, 0, None) != 0
+    assert lib.hipac_train_amp_encoder_forward(None, None, None, 4, 0.1, 1e-5, None, None, 0, None) != 0
+    assert b"train_amp_forward: null argument" in lib.hipac_last_error()
     assert lib.hipac_adam_step(None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 1, None) != 0
     print("asan drive ok")
 """)
