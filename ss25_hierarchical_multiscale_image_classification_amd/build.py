@@ -24,8 +24,7 @@ OBJ = CSRC / os.environ.get("HIPAC_OBJ_DIR", "build")
 LIB = PKG / os.environ.get("HIPAC_LIB_NAME", "libhipac_hip.so")
 SOURCES = ["hipac_capi.hip", "preprocess.hip", "level_planes.hip", "mil.hip", "ntxent.hip", "conv_bf16.hip", "conv_f16.hip",
            "conv_f32.hip", "conv_f16x3.hip", "conv_f16q8.hip", "train.hip", "train_amp.hip", "augment.hip", "jpeg_decode.hip", "froc.hip"]
-HEADERS = ["common.h", "conv_igemm.h", "halo16.h", "halo16x2.h", "e4m3.h", "block16_c64.h", "train_common.h", "../../include/hipac.h",
-           "../../include/hipac_eval.h"]
+PUBLIC_HEADERS = [PKG.parent / "include" / "hipac.h", PKG.parent / "include" / "hipac_eval.h"]
 ARCH = "gfx950"
 # -ffp-contract=off: the host-side Pillow coefficient restatement must round every
 # double operation separately (no fused multiply-add), see preprocess.hip.
@@ -50,7 +49,7 @@ def _stale(target: Path, deps) -> bool:
 def build_library(force: bool = False, verbose: bool = True) -> Path:
     OBJ.mkdir(exist_ok=True)
     hipcc = _hipcc()
-    hdrs = [CSRC / h for h in HEADERS] + [Path(__file__)]
+    hdrs = [*sorted(CSRC.glob("*.h")), *PUBLIC_HEADERS, Path(__file__)]  # every header: none can drop out of the staleness check
     jobs = []
     for src in SOURCES:
         s = CSRC / src

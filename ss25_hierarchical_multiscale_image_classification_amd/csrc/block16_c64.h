@@ -1,5 +1,5 @@
-// block16_c64_kernel: the layer1 BasicBlock (56x56, 64 -> 64 -> 64 channels) in ONE kernel (gfx950), included by conv_igemm.h
-// after halo16.h (Asm16, lds_read16, wait_lgkmcnt, permlane16_swap, perm16):
+// block16_c64_kernel: the layer1 BasicBlock (56x56, 64 -> 64 -> 64 channels) in ONE kernel (gfx950), on the helpers
+// of halo16.h (Asm16, lds_read16, wait_lgkmcnt, permlane16_swap, perm16):
 //     out = relu(conv2(relu(conv1(x) + b1)) + b2 + x)
 // The two 3x3 convolutions of a layer1 block are HBM-bound when launched separately (each streams a
 // 200 MB activation in and out per 512 patches, conv2 a second one for the shortcut: 4.5 - 5 TB/s measured);
@@ -47,6 +47,7 @@
 // The accumulation order differs from conv3x3_c64_kernel's (32 channels per MFMA instead of 16): fused == unfused holds to
 // rounding now, not bit for bit (tests/test_gpu_resnet.py).
 #pragma once
+#include "halo16.h"
 
 namespace hipac {
 

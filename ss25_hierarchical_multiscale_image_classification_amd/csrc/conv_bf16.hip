@@ -1,5 +1,5 @@
 // bf16 instantiation of the ResNet18 trunk (separate TU so the two precisions compile in parallel).
-#include "conv_igemm.h"
+#include "trunk.h"
 namespace hipac {
 int run_trunk_bf16(const Net& net, const Plan& p, char* ws, const void* xin, int n_early, int img_off, int n_late,
                    hipStream_t s, int first, int last) {

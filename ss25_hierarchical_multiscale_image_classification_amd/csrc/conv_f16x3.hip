@@ -1,6 +1,6 @@
 // fp16x3 instantiation of the ResNet18 trunk: (hi, lo) fp16 pairs, three MFMA products per term -- on halo16x2.h's X3 form.
 // The tighter of the two precision modes that meet the reference's fp32 results to 1e-3.
-#include "conv_igemm.h"
+#include "trunk.h"
 namespace hipac {
 int run_trunk_f16x3(const Net& net, const Plan& p, char* ws, const void* xin, int n_early, int img_off, int n_late,
                     hipStream_t s, int first, int last) {

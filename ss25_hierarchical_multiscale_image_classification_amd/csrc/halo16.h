@@ -1,5 +1,5 @@
-// conv3x3_halo16_kernel: the halo direct convolution of conv_igemm.h (3x3 / stride 1 / pad 1, layers 2-4) on
-// v_mfma_f32_16x16x32_{bf16,f16} instead of 32x32x16 (round 4).  Included by conv_igemm.h.
+// conv3x3_halo16_kernel: the halo direct convolution (3x3 / stride 1 / pad 1, layers 2-4; band geometry: conv_device.h,
+// above halo_band_pieces) on v_mfma_f32_16x16x32_{bf16,f16} instead of 32x32x16 (round 4).
 //
 // Why a second MFMA shape: under the whole forward this chip sits at its package power limit (sclk ~1.98 GHz of 2.4,
 // DESIGN.md section 3), so cycles per FLOP do not decide the rate -- the clock the chip can hold does, and the guide
@@ -27,9 +27,16 @@
 // to the SOURCE row of the weight DMA (computed once per tile), which keeps D's rows in natural channel order.
 //
 // Everything else (contiguous band per 64-channel chunk by LDS-DMA, zero slots by parity for image-edge taps, 2-slot weight
-// ring one tap ahead through a buffer descriptor, persistent workgroups, per-wave staged epilogue, folded projection
-// PCIN) is described above halo_band_pieces in conv_igemm.h.
+// ring one tap ahead through a buffer descriptor, persistent workgroups, per-wave staged epilogue) is described above
+// halo_band_pieces in conv_device.h.
+//
+// PCIN > 0 (second conv of a down-sampling BasicBlock): the block's 1x1 / stride 2 projection shortcut is folded in as
+// PCIN / 64 extra K steps -- the "band" of such a step is a GATHER of the block input's pixels (2y, 2x), 64 channels
+// each, placed where the centre tap reads, the weight tile comes from the projection's [COUT][PCIN] matrix, and `bias`
+// is the sum of both biases: conv2 + projection accumulate in ONE fp32 accumulator, the shortcut map (one HBM round
+// trip) and the projection launch disappear.  `resid` is then the block input [n][2H][2W][PCIN], `wgt_p` the projection.
 #pragma once
+#include "conv_device.h"
 
 namespace hipac {
 

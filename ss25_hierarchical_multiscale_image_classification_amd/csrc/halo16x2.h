@@ -1,6 +1,6 @@
 // conv3x3_halo16x2_kernel: every 3x3 convolution (stride 1, and the stride-2 entry convs with the projection shortcut folded into
 // the block's second conv) of the two parity modes -- `fp16q8` (round 4; VERDICT r3 item 3 "a parity mode with cheaper cross
-// terms"), described first, and `fp16x3` (the X3 form, at the template's comment).  Included by conv_igemm.h after halo16.h, whose
+// terms"), described first, and `fp16x3` (the X3 form, at the template's comment).  Built on halo16.h, whose
 // tile, band, weight ring, lane -> pixel permutation, written-out MFMA stream and direct epilogue it shares -- read that header first.
 //
 // Arithmetic.  As in fp16x3 every value is the pair hi = rn16(v), lo = rn16(v - hi) of fp16 numbers and a product is
@@ -24,6 +24,7 @@
 // K loop.  Per 64-channel chunk c: the hi band (pair tensor, chunk c of the hi plane), 9 taps of 64 f16 MFMAs; then the q8 band of
 // chunk c, 9 taps of 32 fp8 MFMAs of twice the cycles: 2 MFMA-time units per term where fp16x3 spends 3.
 #pragma once
+#include "halo16.h"
 
 #ifndef HIPAC_Q8_ABL
 #define HIPAC_Q8_ABL 0  // developer builds (wrong results): 1 no epilogue arithmetic / stores, 2 no residual pass, 4 no fp8 steps, 8 no f16 steps, 16 epilogue arithmetic but no pair / byte stores

@@ -2,7 +2,7 @@
 // backward as hand-written HIP, fp32 throughout (the reference's pretrain_simclr runs fp32 without
 // autocast, src/models/simclr.py:85-96), convolutions on the exact f32 MFMA (v_mfma_f32_32x32x2_f32).
 //
-//   forward   conv (implicit GEMM, the v1 kernel of conv_igemm.h on re-packed weights) -> batch statistics
+//   forward   conv (implicit GEMM, the v1 kernel, conv_v1.h, on re-packed weights) -> batch statistics
 //             (fp64 per-workgroup partial sums added in a fixed order, no atomics) -> normalise (+ residual) (+ ReLU);
 //             3x3/2 max-pool with saved arg-max; global average pool.  Pre-BN and post-activation maps of every conv are
 //             kept for the backward.
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ w
   if (mode == 0) dst[(size_t)co * ks * ks * cin + (size_t)(kh * ks + kw) * cin + ci] = v;
   else if (mode == 1) dst[(size_t)ci * ks * ks * cout + (size_t)((ks - 1 - kh) * ks + ks - 1 - kw) * cout + co] = v;
   else if (mode == 3) {
-    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2, conv_igemm.h): class (py, px) = (kh != 1, kw != 1),
+    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2, conv_launch.h): class (py, px) = (kh != 1, kw != 1),
     // taps (a, b) = ((2 - kh) / 2, (2 - kw) / 2); blocks of 1, 2, 2, 4 taps back to back, each [ci][tap][co]
     const int py = kh != 1, px = kw != 1, a = py ? (2 - kh) / 2 : 0, b = px ? (2 - kw) / 2 : 0;
     const int ntap = (py ? 2 : 1) * (px ? 2 : 1), tap = a * (px ? 2 : 1) + b;

@@ -4,7 +4,7 @@
 // master parameters / gradients / Adam state (the flat buffers of train.hip, unchanged), a loss scale owned by the
 // caller (train_native.GradScaler) -- as hand-written HIP:
 //
-//   forward   weights re-packed fp32 -> fp16 per step; convolutions on the inference kernels of conv_igemm.h (halo
+//   forward   weights re-packed fp32 -> fp16 per step; convolutions on the inference kernels behind conv_launch.h (halo
 //             kernel for 3x3 / stride 1, LDS-DMA kernel for stride 2 and 1x1, v1 kernel for the stem) with a zero
 //             bias and no ReLU; batch statistics from the fp16 map in fp64, two-stage and DETERMINISTIC (per
 //             workgroup partials, summed in a fixed order); normalise (+ residual) (+ ReLU) fp16 -> fp16.
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void pack_w_h_kernel(const float* __restrict__
   if (mode == 0) dst[(size_t)co * ks * ks * cin + (size_t)(kh * ks + kw) * cin + ci] = v;
   else if (mode == 1) dst[(size_t)ci * ks * ks * cout + (size_t)((ks - 1 - kh) * ks + ks - 1 - kw) * cout + co] = v;
   else if (mode == 3) {
-    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2, conv_igemm.h): class (py, px) = (kh != 1, kw != 1),
+    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2, conv_launch.h): class (py, px) = (kh != 1, kw != 1),
     // its taps (a, b) = ((2 - kh) / 2, (2 - kw) / 2) -- tap a = 0 is the coarse row of the output position itself (kh = 2), a = 1 the
     // row below (kh = 0); blocks of 1, 2, 2, 4 taps back to back, each [ci][tap][co]
     const int py = kh != 1, px = kw != 1, a = py ? (2 - kh) / 2 : 0, b = px ? (2 - kw) / 2 : 0;

@@ -10,7 +10,7 @@
 //   conv_wgrad                 weight gradient of conv i into the flat gradient buffer
 //   maxpool, maxpool_bwd, avgpool, avgpool_bwd, add_mask   the pool and ReLU-mask launches (their thread geometries differ)
 #pragma once
-#include "conv_igemm.h"
+#include "conv_launch.h"
 
 namespace hipac {
 
