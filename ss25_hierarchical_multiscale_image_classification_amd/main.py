@@ -21,7 +21,12 @@ slides, ``--train*`` the batches; started by this program itself before it touch
 ``features.save_froc_csv``) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
 
-Everything else outside the hot path (download, plots, MIL) is out of scope and the
+``--train_mil`` trains the ABMIL slide classifier (``mil_train.py``, the loop of the reference's
+``experiments/experiment_configs.yaml``) on the ``patch_features_L.npy`` / ``patch_labels_L.npy`` / ``patch_paths_L.txt``
+triple of ``--patch_level L`` in the working directory and writes ``models/mil_model.pth`` and ``results/metrics.json``;
+``--predict_mil`` scores every bag of the triple with ``--mil_model`` into ``results/mil_predictions.csv``.
+
+Everything else outside the hot path (download, plots) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
 """
 from __future__ import annotations
@@ -91,6 +96,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "training pool (implies the device input pipeline)")
     p.add_argument("--simclr_precision", choices=["fp16", "fp32"], default="fp32",
                    help="arithmetic of the SimCLR pre-training step (the reference's loop is fp32, src/models/simclr.py:85-96)")
+    p.add_argument("--train_mil", action="store_true",
+                   help="train the MIL slide classifier on the feature triple of --patch_level in the working directory "
+                        "(under --world_size N rank 0 trains: the step is small and is not sharded)")
+    p.add_argument("--predict_mil", action="store_true",
+                   help="score every bag of the feature triple with --mil_model -> results/mil_predictions.csv (rank 0)")
+    p.add_argument("--mil_pooling", choices=["attention", "mean", "max"], default="attention")
+    p.add_argument("--mil_by_slide", action="store_true", help="one bag per slide (default: the reference's key, one per slide column)")
+    p.add_argument("--mil_epochs", type=int, default=50)
+    p.add_argument("--mil_bag_size", type=int, default=None, help="sample at most this many patches per bag and epoch (default: the whole bag)")
+    p.add_argument("--mil_bags_per_step", type=int, default=32)
+    p.add_argument("--mil_model", type=str, default=os.path.join("models", "mil_model.pth"))
     p.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)
     return p
 
@@ -286,6 +302,42 @@ def cmd_run_evaluation(args):
     return run_evaluation(data_root(args))
 
 
+def mil_triple(args):
+    """(features, labels, paths) file names of the one level --patch_level names, or None after a message."""
+    if args.patch_level == "all":
+        print("[ERROR] --train_mil / --predict_mil work on one level: give --patch_level 0, 1, 2 or 3, not 'all'.")
+        return None
+    level = int(args.patch_level)
+    triple = (f"patch_features_{level}.npy", f"patch_labels_{level}.npy", f"patch_paths_{level}.txt")
+    missing = [f for f in triple if not os.path.exists(f)]
+    if missing:
+        print(f"[ERROR] {', '.join(missing)} not found: run --extract_features --patch_level {level} first.")
+        return None
+    return triple
+
+
+def cmd_mil(args, train: bool):
+    triple = mil_triple(args)  # before anything touches a GPU
+    if triple is None:
+        return 2
+    from .dist import rank_world
+
+    if rank_world()[0] != 0:  # not sharded: rank 0 does it
+        return 0
+    from . import mil_train
+
+    if train:
+        mil_train.train_mil(*triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, epochs=args.mil_epochs,
+                            bags_per_step=args.mil_bags_per_step, bag_size=args.mil_bag_size,
+                            seed=0 if args.seed is None else args.seed, max_steps=args.max_steps)
+        return 0
+    if not os.path.exists(args.mil_model):
+        print(f"[ERROR] {args.mil_model} not found: run --train_mil first or give --mil_model PATH.")
+        return 2
+    mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide)
+    return 0
+
+
 def _seed_everything(seed: int):
     import random
 
@@ -301,6 +353,9 @@ def main(argv=None) -> int:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")
             return 2
+    if (args.train_mil or args.predict_mil) and args.patch_level == "all":
+        mil_triple(args)  # prints why; refused before any process is started or any GPU touched
+        return 2
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.world_size > 1 and not under_launcher:
         # parent: start one fresh process per GPU and supervise them; nothing here may initialise the GPU
@@ -350,6 +405,11 @@ def _dispatch(args) -> int:
         rc = cmd_train(args, args.strategy) or rc
     if args.run_evaluation:
         rc = cmd_run_evaluation(args) or rc
+    if args.train_mil:
+        _rendezvous()
+        rc = cmd_mil(args, True) or rc
+    if args.predict_mil:
+        rc = cmd_mil(args, False) or rc
     return rc
 
 

@@ -1,0 +1,360 @@
+"""Training of the ABMIL slide classifier on the device (``--train_mil`` / ``--predict_mil``).
+
+The reference has the model (src/models/mil_classifier.py) and the bag dataset (src/datasets/mildataset.py) but never
+wired a loop into its ``main.py``; ``experiments/experiment_configs.yaml`` says what the loop is (Adam, lr 1e-3, weight
+decay 1e-4, 50 epochs, 32 bags per step, early stopping with patience 5, a 0.8 / 0.1 / 0.1 split, 100 patches per bag,
+``models/mil_model.pth``, ``results/metrics.json``) and ``src/utils/metrics.py`` what the metrics are.
+
+* ``NativeMILTrainer``: the parameters in one flat fp32 buffer (``train_native.FlatAdam``); one step = one
+  ``hipac_mil_train_fwd_bwd`` (include/hipac_mil_train.h, ``csrc/mil_train.hip``) over a batch of ragged bags that are
+  rows of the resident feature matrix, the L2 term, ``hipac_adam_step``.
+* ``train_mil`` / ``predict_mil``: the loop and the scoring over the (features, labels, paths) triple that
+  ``--extract_features`` writes.  Validation and prediction go through ``MILClassifier.forward_bags``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import capi
+from .mil import MILClassifier, group_patches_by_wsi
+from .train_native import FlatAdam
+
+MIL_TRAIN_ABI_VERSION = 1  # include/hipac_mil_train.h HIPAC_MIL_TRAIN_ABI_VERSION this binding was written against
+
+# name -> (restype, argtypes); must list every symbol include/hipac_mil_train.h declares (tests/test_mil_train_capi_symbols.py)
+MIL_TRAIN_SYMBOLS = {
+    "hipac_mil_train_abi_version": (C.c_int, []),
+    "hipac_mil_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "hipac_mil_train_fwd_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_size_t, C.c_int, C.c_void_p]),
+    "hipac_mil_train_l2_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+}
+
+_bound = None
+
+
+def load_mil_train_library():
+    """The library of ``capi.load_library()`` with the MIL training entry points bound; HipacError on a version mismatch."""
+    global _bound
+    lib = capi.load_library()
+    if _bound is not lib:
+        for name, (res, args) in MIL_TRAIN_SYMBOLS.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.hipac_mil_train_abi_version() != MIL_TRAIN_ABI_VERSION:
+            raise capi.HipacError(f"MIL training ABI version mismatch: library {lib.hipac_mil_train_abi_version()}, "
+                                  f"binding {MIL_TRAIN_ABI_VERSION}")
+        _bound = lib
+    return lib
+
+
+# state_dict key -> hipac_mil_params_t field, in the order of the flat buffer
+PARAM_FIELDS = (("aggregator.attn_V.weight", "attn_V_w"), ("aggregator.attn_V.bias", "attn_V_b"),
+                ("aggregator.attn_U.weight", "attn_U_w"), ("aggregator.attn_U.bias", "attn_U_b"),
+                ("classifier.0.weight", "fc1_w"), ("classifier.0.bias", "fc1_b"),
+                ("classifier.2.weight", "fc2_w"), ("classifier.2.bias", "fc2_b"))
+
+
+class NativeMILTrainer:
+    """``MILClassifier`` under torch.optim.Adam(lr, weight_decay) with the whole step in HIP.  ``sd``: a MILClassifier
+    state_dict (any device, converted to float32); the parameters live in one flat buffer, every tensor starting on a
+    16-byte boundary (the gaps stay 0)."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], pooling: str, device, lr: float = 1e-3, weight_decay: float = 1e-4,
+                 class_weights=None):
+        if pooling not in capi.MIL_POOLING:
+            raise ValueError("Unknown pooling: choose from 'attention', 'mean', 'max'")
+        self.lib = load_mil_train_library()
+        self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
+        if self.device.type != "cuda":
+            raise capi.HipacError("NativeMILTrainer needs a ROCm device: there is no CPU fallback")
+        self.keys = [k for k, _ in PARAM_FIELDS if pooling == "attention" or not k.startswith("aggregator.")]
+        missing = [k for k in self.keys if k not in sd]
+        if missing:
+            raise capi.HipacError(f"state_dict lacks {missing}")
+        self.shapes = {k: tuple(sd[k].shape) for k in self.keys}
+        self.offsets, o = {}, 0
+        for k in self.keys:
+            self.offsets[k] = o
+            o += (int(np.prod(self.shapes[k])) + 3) // 4 * 4
+        self.opt = FlatAdam(o, self.device, lr)
+        for k in self.keys:
+            self._view(self.opt.params, k).copy_(sd[k].detach().to(self.device, torch.float32))
+        self.F, self.hidden = int(self.shapes["classifier.0.weight"][1]), int(self.shapes["classifier.0.weight"][0])
+        self.C = int(self.shapes["classifier.2.weight"][0])
+        self.A = int(self.shapes["aggregator.attn_V.weight"][0]) if pooling == "attention" else 0
+        if pooling == "attention" and self.shapes["aggregator.attn_V.weight"] != (self.A, self.F):
+            raise capi.HipacError("aggregator.attn_V.weight does not match feature_dim")
+        if self.shapes["classifier.2.weight"] != (self.C, self.hidden):
+            raise capi.HipacError("classifier.2.weight does not match classifier.0.weight")
+        self._p, self._g = self._struct(self.opt.params), self._struct(self.opt.grads)
+        self.class_weights = None if class_weights is None else \
+            torch.as_tensor(class_weights, dtype=torch.float32).to(self.device).contiguous()
+        if self.class_weights is not None and self.class_weights.numel() != self.C:
+            raise capi.HipacError(f"class_weights must have {self.C} entries")
+        self._ws: Optional[torch.Tensor] = None
+        self.attn: Optional[torch.Tensor] = None
+
+    def _view(self, flat: torch.Tensor, key: str) -> torch.Tensor:
+        o = self.offsets[key]
+        return flat[o:o + int(np.prod(self.shapes[key]))].view(self.shapes[key])
+
+    def _struct(self, flat: torch.Tensor) -> capi.MilParams:
+        p = capi.MilParams()
+        for k, field in PARAM_FIELDS:
+            if k in self.offsets:
+                setattr(p, field, flat.data_ptr() + 4 * self.offsets[k])
+        p.feature_dim, p.attn_dim, p.hidden_dim, p.num_classes = self.F, self.A, self.hidden, self.C
+        return p
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The reference's key names; loads into its MILClassifier and into ``mil.MILClassifier`` with strict=True."""
+        return {k: self._view(self.opt.params, k).clone() for k in self.keys}
+
+    def grad_dict(self) -> Dict[str, torch.Tensor]:
+        return {k: self._view(self.opt.grads, k).clone() for k in self.keys}
+
+    def forward_backward(self, feats: torch.Tensor, rows, offsets, labels, accumulate: bool = False, want_attn: bool = False
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """feats float32[N, F] on the device (stays in place); rows int[n] indices into it, or None for
+        the identity (then offsets must end at N); offsets int[n_bags + 1]; labels int64[n_bags] -> (loss float32[], logits[n_bags, C]);
+        the gradients land in the flat buffer (``grad_dict``).  Everything is checked on the host before the launch: a
+        bad row index never reaches a kernel."""
+        if not torch.is_tensor(feats) or not feats.is_cuda:
+            raise capi.HipacError("HIP path called with a CPU tensor: there is no CPU fallback (move inputs to cuda)")
+        if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous() or feats.device != self.device:
+            raise capi.HipacError(f"feats must be a contiguous float32[N, feature_dim] tensor on {self.device}")
+        N, F = int(feats.shape[0]), int(feats.shape[1])
+        if F != self.F:
+            raise capi.HipacError(f"feats has {F} columns, the model {self.F}")
+        offs = np.asarray(offsets.detach().cpu() if torch.is_tensor(offsets) else offsets).astype(np.int64).ravel()
+        if offs.size < 2 or offs[0] != 0 or bool((offs[1:] <= offs[:-1]).any()):
+            raise capi.HipacError("offsets must start at 0 and increase strictly (no empty bags)")
+        n, n_bags = int(offs[-1]), offs.size - 1
+        if rows is None:
+            if n > N:
+                raise capi.HipacError(f"offsets cover {n} rows, feats has {N}")
+            if n != N:
+                raise capi.HipacError(f"offsets must end at the number of rows ({N}), got {n}")
+            rows_dev = None
+        else:
+            r = torch.as_tensor(rows)
+            if r.dim() != 1 or r.dtype not in (torch.int32, torch.int64):
+                raise capi.HipacError("rows must be a 1-d int32 / int64 index")
+            if int(r.numel()) != n:
+                raise capi.HipacError(f"offsets must end at the number of rows ({int(r.numel())}), got {n}")
+            if n and (int(r.min()) < 0 or int(r.max()) >= N):
+                raise capi.HipacError(f"rows holds an index outside [0, {N})")
+            rows_dev = r.to(self.device, torch.int32).contiguous()
+        lab = torch.as_tensor(labels)
+        if lab.dim() != 1 or int(lab.numel()) != n_bags or lab.dtype != torch.int64:
+            raise capi.HipacError(f"labels must be int64[{n_bags}]")
+        if n_bags and (int(lab.min()) < 0 or int(lab.max()) >= self.C):
+            raise capi.HipacError(f"labels holds a class outside [0, {self.C})")
+        lab = lab.to(self.device).contiguous()
+        offs_dev = torch.from_numpy(offs.astype(np.int32)).to(self.device)
+        pool = capi.MIL_POOLING[self.pooling]
+        need = self.lib.hipac_mil_train_workspace_bytes(C.addressof(self._p), pool, n, n_bags)
+        if need == 0:
+            raise capi.HipacError(f"mil training step of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        logits = torch.empty((n_bags, self.C), dtype=torch.float32, device=self.device)
+        self.attn = torch.empty(n, dtype=torch.float32, device=self.device) if (want_attn and self.pooling == "attention") else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.hipac_mil_train_fwd_bwd(
+                C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
+                lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
+                capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0, capi._stream())
+        capi._check(rc, "hipac_mil_train_fwd_bwd")
+        return loss, logits
+
+    def step(self, feats, rows, offsets, labels) -> Tuple[torch.Tensor, torch.Tensor]:
+        """forward_backward, the L2 term (g += weight_decay * p, torch-Adam's form), one Adam update."""
+        loss, logits = self.forward_backward(feats, rows, offsets, labels)
+        if self.weight_decay != 0.0:
+            with torch.cuda.device(self.device):
+                capi._check(self.lib.hipac_mil_train_l2_add(self.opt.grads.data_ptr(), self.opt.params.data_ptr(),
+                                                            self.opt.params.numel(), self.weight_decay, capi._stream()),
+                            "hipac_mil_train_l2_add")
+        self.opt.step()
+        return loss, logits
+
+
+# ----------------------------------------------------------------------------
+# host side of the loop: split, epoch batches, metrics
+# ----------------------------------------------------------------------------
+def split_bags(n_bags: int, seed: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """A seeded permutation of the bags cut 0.8 / 0.1 / 0.1 -> (train, val, test) bag indices.  Train gets at least one
+    bag; val and test get int(0.1 n) each (so both are empty below 10 bags) and train the rest."""
+    if n_bags < 1:
+        raise ValueError("no bags to split")
+    perm = np.random.default_rng(seed).permutation(n_bags)
+    n_val = n_test = int(0.1 * n_bags)
+    n_train = n_bags - n_val - n_test
+    return perm[:n_train], perm[n_train:n_train + n_val], perm[n_train + n_val:]
+
+
+def epoch_batches(train_bags: Sequence[int], order: np.ndarray, offsets: np.ndarray, epoch: int, seed: int = 0,
+                  bags_per_step: int = 32, bag_size: Optional[int] = None):
+    """The steps of one epoch: a seeded shuffle of the training bags, cut into groups of ``bags_per_step``; with
+    ``bag_size`` a seeded sample without replacement of at most that many rows of each bag (in the bag's own order).
+    Yields (rows int32[n] into the feature matrix, offsets int64[k + 1], bag indices int64[k]).  A function of
+    (seed, epoch) only."""
+    rng = np.random.default_rng([seed, epoch + 1])
+    bags = np.asarray(train_bags, np.int64)[rng.permutation(len(train_bags))]
+    for s in range(0, len(bags), bags_per_step):
+        group = bags[s:s + bags_per_step]
+        rows, offs = [], [0]
+        for b in group:
+            r = order[offsets[b]:offsets[b + 1]]
+            if bag_size is not None and len(r) > bag_size:
+                r = r[np.sort(rng.choice(len(r), size=bag_size, replace=False))]
+            rows.append(r)
+            offs.append(offs[-1] + len(r))
+        yield np.concatenate(rows).astype(np.int32), np.asarray(offs, np.int64), group
+
+
+def classification_metrics(y_true, y_pred) -> Dict[str, object]:
+    """src/utils/metrics.py: accuracy, precision / recall / F1 of class 1 (0.0 where a denominator is 0) and the
+    confusion matrix, as plain Python numbers."""
+    t, p = np.asarray(y_true).astype(np.int64).ravel(), np.asarray(y_pred).astype(np.int64).ravel()
+    tp, tn = int(((t == 1) & (p == 1)).sum()), int(((t == 0) & (p == 0)).sum())
+    fp, fn = int(((t == 0) & (p == 1)).sum()), int(((t == 1) & (p == 0)).sum())
+    prec = tp / (tp + fp) if tp + fp > 0 else 0.0
+    rec = tp / (tp + fn) if tp + fn > 0 else 0.0
+    return {"accuracy": float((t == p).mean()) if t.size else 0.0, "precision": float(prec), "recall": float(rec),
+            "f1_score": float(2 * prec * rec / (prec + rec)) if prec + rec > 0 else 0.0,
+            "confusion_matrix": {"TP": tp, "TN": tn, "FP": fp, "FN": fn}}
+
+
+def load_triple(features_path, labels_path, paths_path, by_slide: bool = False):
+    """-> (features float32[N, F], order, offsets, bag names, bag labels) of the files ``--extract_features`` writes."""
+    feats = np.load(features_path)
+    labels = np.load(labels_path)
+    with open(paths_path, "r") as f:
+        paths = [line.strip() for line in f if line.strip()]
+    if feats.ndim != 2 or len(paths) != feats.shape[0] or labels.shape[0] != feats.shape[0]:
+        raise ValueError(f"triple does not agree: features {feats.shape}, labels {labels.shape}, {len(paths)} paths")
+    order, offsets, names, wsi = group_patches_by_wsi(paths, labels, by_slide)
+    return np.ascontiguousarray(feats, dtype=np.float32), order, offsets, names, wsi
+
+
+def initial_state_dict(feature_dim: int, pooling: str, seed: int) -> Dict[str, torch.Tensor]:
+    """MILClassifier's own (torch default) initialisation under ``torch.manual_seed(seed)``, drawn on the CPU."""
+    gen_state = torch.get_rng_state()
+    torch.manual_seed(seed)
+    try:
+        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling).state_dict().items()}
+    finally:
+        torch.set_rng_state(gen_state)
+
+
+def _gathered(feats_dev: torch.Tensor, bags, order, offsets):
+    """Contiguous copy of the rows of ``bags`` (made once for the val / test split: forward_bags wants bag rows contiguous)."""
+    rows = np.concatenate([order[offsets[b]:offsets[b + 1]] for b in bags])
+    offs = np.concatenate([[0], np.cumsum([offsets[b + 1] - offsets[b] for b in bags])]).astype(np.int64)
+    return feats_dev[torch.from_numpy(rows).to(feats_dev.device)].contiguous(), offs
+
+
+def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray) -> torch.Tensor:
+    model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling).to(feats.device)
+    model.load_state_dict(sd, strict=True)
+    model.eval()
+    return model.forward_bags(feats, offs)[0]
+
+
+def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False, epochs: int = 50,
+              bags_per_step: int = 32, bag_size: Optional[int] = None, lr: float = 1e-3, weight_decay: float = 1e-4,
+              patience: int = 5, seed: int = 0, out_dir: str = ".", max_steps: Optional[int] = None, device=None) -> Dict[str, object]:
+    """The yaml's loop (module docstring).  Writes ``<out_dir>/models/mil_model.pth`` (the state with the best validation
+    loss; the last one when there is no validation split) and ``<out_dir>/results/metrics.json``; returns the metrics."""
+    feats, order, offsets, names, wsi = load_triple(features_path, labels_path, paths_path, by_slide)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    tr, va, te = split_bags(len(names), seed)
+    print(f"[INFO] MIL: {len(names)} bags of {feats.shape[0]} patches; train / val / test = {len(tr)} / {len(va)} / {len(te)}")
+    if len(va) == 0:
+        print("[INFO] MIL: the validation split is empty: early stopping is off")
+    feats_dev = torch.from_numpy(feats).to(dev)  # uploaded once; every step reads it in place through a row index
+    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed), pooling, dev, lr=lr, weight_decay=weight_decay)
+    labels_all = torch.from_numpy(wsi)
+    val = _gathered(feats_dev, va, order, offsets) if len(va) else None
+    val_labels = labels_all[torch.from_numpy(va)].to(dev) if len(va) else None
+    history = {"train_loss": [], "val_loss": []}
+    best, best_sd, bad, steps, stopped = float("inf"), None, 0, 0, False
+    for epoch in range(epochs):
+        losses = []
+        for rows, offs, group in epoch_batches(tr, order, offsets, epoch, seed, bags_per_step, bag_size):
+            loss, _ = trainer.step(feats_dev, rows, offs, labels_all[torch.from_numpy(group)])
+            losses.append(loss)
+            steps += 1
+            if max_steps is not None and steps >= max_steps:
+                break
+        history["train_loss"].append(float(torch.stack(losses).mean().item()))
+        msg = f"[INFO] MIL epoch {epoch + 1}/{epochs}: train loss {history['train_loss'][-1]:.6f}"
+        if val is not None:
+            v = float(torch.nn.functional.cross_entropy(_score(trainer.state_dict(), pooling, *val), val_labels).item())
+            history["val_loss"].append(v)
+            msg += f", val loss {v:.6f}"
+            if v < best:
+                best, best_sd, bad = v, trainer.state_dict(), 0
+            else:
+                bad += 1
+        print(msg)
+        if max_steps is not None and steps >= max_steps:
+            break
+        if val is not None and bad >= patience:
+            print(f"[INFO] MIL: early stopping after epoch {epoch + 1} (no better validation loss for {patience} epochs)")
+            stopped = True
+            break
+    if best_sd is None:
+        best_sd = trainer.state_dict()
+    os.makedirs(os.path.join(out_dir, "models"), exist_ok=True)
+    os.makedirs(os.path.join(out_dir, "results"), exist_ok=True)
+    model_path = os.path.join(out_dir, "models", "mil_model.pth")
+    torch.save({k: v.cpu() for k, v in best_sd.items()}, model_path)
+    if len(te):
+        tf, toffs = _gathered(feats_dev, te, order, offsets)
+        pred = _score(best_sd, pooling, tf, toffs).argmax(1).cpu().numpy()
+        metrics = classification_metrics(wsi[te], pred)
+    else:
+        print("[INFO] MIL: the test split is empty: the metrics are those of no predictions")
+        metrics = classification_metrics([], [])
+    metrics.update({"train_loss": history["train_loss"], "val_loss": history["val_loss"], "epochs_run": len(history["train_loss"]),
+                    "steps": steps, "early_stopped": stopped, "pooling": pooling,
+                    "split_sizes": {"train": int(len(tr)), "val": int(len(va)), "test": int(len(te))}})
+    with open(os.path.join(out_dir, "results", "metrics.json"), "w") as f:
+        json.dump(metrics, f, indent=2)
+    print(f"[INFO] MIL: model saved to {model_path}; test accuracy {metrics['accuracy']:.4f}")
+    return metrics
+
+
+def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False,
+                out_dir: str = ".", device=None) -> List[Tuple[str, float, int]]:
+    """Every bag of the triple scored with a saved model -> [(bag name, probability of class 1, predicted label)], also
+    written as ``<out_dir>/results/mil_predictions.csv``."""
+    feats, order, offsets, names, _ = load_triple(features_path, labels_path, paths_path, by_slide)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    sd = {k: v.to(dev, torch.float32).contiguous() for k, v in torch.load(model_path, map_location="cpu", weights_only=True).items()}
+    feats_dev = torch.from_numpy(feats).to(dev)
+    f, offs = _gathered(feats_dev, np.arange(len(names)), order, offsets)
+    logits = _score(sd, pooling, f, offs)
+    prob = torch.softmax(logits, dim=1)[:, 1].cpu().numpy()
+    pred = logits.argmax(1).cpu().numpy()
+    out = [(n, float(p), int(y)) for n, p, y in zip(names, prob, pred)]
+    os.makedirs(os.path.join(out_dir, "results"), exist_ok=True)
+    with open(os.path.join(out_dir, "results", "mil_predictions.csv"), "w") as fh:
+        fh.write("bag,probability,prediction\n")
+        for n, p, y in out:
+            fh.write(f"{n},{p:.6f},{y}\n")
+    print(f"[INFO] MIL: {len(out)} bags scored -> {os.path.join(out_dir, 'results', 'mil_predictions.csv')}")
+    return out
