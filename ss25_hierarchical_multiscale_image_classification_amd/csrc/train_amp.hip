@@ -14,421 +14,16 @@
 //             read TRANSPOSED from LDS by ds_read_b64_tr_b16, split-K partials in fp32 summed in a fixed order (no
 //             atomics: a step run twice gives the same bits).
 // The gradients that arrive (dfeats) and leave (grads) carry the caller's loss scale.  The host driver of the forward
-// and backward is shared with train.hip (train_common.h); this file supplies the fp16 kernels, the workspace plan and the
-// Fp16Step precision struct.
+// and backward, the workspace plan and the launches of the small kernels are shared with train.hip (train_common.h); the
+// small kernels themselves (weight packing, batch norm, pools, ReLU masks, the sum of the split-K partials) are templates
+// over the element type in train_kernels.h.  This file supplies the fp16 weight-gradient kernel, the gradient unscale /
+// finiteness check and the Fp16Step precision struct.
 #include "train_common.h"
 
 namespace hipac {
 
 typedef _Float16 h16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-static size_t wpack_offset_h(int i) {
-  size_t o = 0;
-  for (int k = 0; k < i; ++k) o += (packed_w_floats(k) + 127) & ~(size_t)127;  // 256-byte aligned rows of the table
-  return o;
-}
-constexpr size_t kWgPartBytes = (size_t)160 << 20;
-
-static TrainPlan make_amp_plan(int B) {
-  TrainPlan p{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t b = (size_t)B;
-  p.xin = take(b * kPadH * kPadW * 4 * 2);
-  size_t maxact = 0, maxw = 0;
-  for (int i = 0; i < kNumConvs; ++i) {
-    const size_t n = b * kConvs[i].hout * kConvs[i].hout * kConvs[i].cout;
-    p.pre[i] = take(n * 2);
-    p.post[i] = take(n * 2);
-    if (n > maxact) maxact = n;
-    if (packed_w_floats(i) > maxw) maxw = packed_w_floats(i);
-  }
-  p.pool = take(b * 56 * 56 * 64 * 2);
-  p.pool_idx = take(b * 56 * 56 * 64);
-  p.mean_rstd = take(stat_offset(kNumConvs) * 4);
-  p.red = take((size_t)kRedBlocks * 1024 * 8);
-  p.sums = take(1024 * 8);
-  const size_t wpack = take(wpack_offset_h(kNumConvs) * 2);
-  for (int i = 0; i < kNumConvs; ++i) p.wpack[i] = wpack + wpack_offset_h(i) * 2;
-  p.wpack_d = take(maxw * 2);
-  p.wgrad_p = take(kWgPartBytes);
-  p.zero_bias = take(512 * 4);
-  p.zero_page = take(256);
-  for (int k = 0; k < 3; ++k) p.g[k] = take(maxact * 2);
-  p.up = take(b * 56 * 56 * 128 * 2);
-  p.total = off;
-  return p;
-}
-
-// ---------------------------------------------------------------------------------------------
-// small kernels (fp16 storage, fp32 / fp64 arithmetic)
-// ---------------------------------------------------------------------------------------------
-// fp32 [co][ci][kh][kw] -> fp16: mode 0 forward [co][(kh,kw)][ci], 1 data gradient [ci][flipped (kh,kw)][co], 2 stem [co][kh*32+kw*4+ci],
-// 3 data gradient of a 3x3 / stride 2 conv, four parity-class blocks
-__global__ __launch_bounds__(256) void pack_w_h_kernel(const float* __restrict__ w, h16* __restrict__ dst, int cout, int cin,
-                                                       int ks, int mode) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (long long)cout * cin * ks * ks) return;
-  const int kw = (int)(gid % ks);
-  long long t = gid / ks;
-  const int kh = (int)(t % ks);
-  t /= ks;
-  const int ci = (int)(t % cin), co = (int)(t / cin);
-  const h16 v = (h16)w[gid];
-  if (mode == 0) dst[(size_t)co * ks * ks * cin + (size_t)(kh * ks + kw) * cin + ci] = v;
-  else if (mode == 1) dst[(size_t)ci * ks * ks * cout + (size_t)((ks - 1 - kh) * ks + ks - 1 - kw) * cout + co] = v;
-  else if (mode == 3) {
-    // data gradient of a 3x3 / stride 2 conv by parity class (launch_dgrad_s2, conv_launch.h): class (py, px) = (kh != 1, kw != 1),
-    // its taps (a, b) = ((2 - kh) / 2, (2 - kw) / 2) -- tap a = 0 is the coarse row of the output position itself (kh = 2), a = 1 the
-    // row below (kh = 0); blocks of 1, 2, 2, 4 taps back to back, each [ci][tap][co]
-    const int py = kh != 1, px = kw != 1, a = py ? (2 - kh) / 2 : 0, b = px ? (2 - kw) / 2 : 0;
-    const int ntap = (py ? 2 : 1) * (px ? 2 : 1), tap = a * (px ? 2 : 1) + b;
-    const size_t blk = (size_t)cin * cout, off = (py ? 3 : 0) * blk + (px ? (py ? 2 : 1) : 0) * blk;
-    dst[off + (size_t)ci * ntap * cout + (size_t)tap * cout + co] = v;
-  } else dst[(size_t)co * 224 + kh * 32 + kw * 4 + ci] = v;
-}
-
-__device__ __forceinline__ void ld8(const h16* p, float (&v)[8]) {
-  const f16x8 t = *reinterpret_cast<const f16x8*>(p);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
-}
-__device__ __forceinline__ void st8(h16* p, const float (&v)[8]) {
-  f16x8 t;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) t[e] = (h16)v[e];
-  *reinterpret_cast<f16x8*>(p) = t;
-}
-
-// Two per-channel sums over the M rows of [M][C] maps, 8 channels per thread, fp64, NO atomics: workgroup b leaves its
-// partial sums in part[b][0..C) and part[b][512..512+C).  MODE 0: (sum x, sum x^2).  MODE 1 (BN backward): (sum dy,
-// sum dy * xhat) with dy masked by (ymask > 0) when given.
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_reduce_h_kernel(const h16* __restrict__ a, const h16* __restrict__ x,
-                                                          const h16* __restrict__ ymask, long long M, int C,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          double* __restrict__ part) {
-  const int c8 = C >> 3, rows_per_pass = 256 / c8, tid = threadIdx.x, g = tid % c8, rsub = tid / c8;
-  double s[8], q[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s[k] = q[k] = 0.0;
-  if (rsub < rows_per_pass) {
-    float mu[8], rs[8];
-    if (MODE == 1) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) mu[k] = mean[8 * g + k], rs[k] = rstd[8 * g + k];
-    }
-    const long long step = (long long)gridDim.x * rows_per_pass;
-    long long r = (long long)blockIdx.x * rows_per_pass + rsub;
-    if (MODE == 0) {
-      // four rows in flight per thread (the pass is a chain of dependent 16-byte loads otherwise: 3.2 TB/s), added in row order
-      for (; r + 3 * step < M; r += 4 * step) {
-        float v0[8], v1[8], v2[8], v3[8];
-        ld8(a + r * C + 8 * g, v0), ld8(a + (r + step) * C + 8 * g, v1), ld8(a + (r + 2 * step) * C + 8 * g, v2), ld8(a + (r + 3 * step) * C + 8 * g, v3);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          s[k] += v0[k], q[k] += (double)v0[k] * v0[k];
-          s[k] += v1[k], q[k] += (double)v1[k] * v1[k];
-          s[k] += v2[k], q[k] += (double)v2[k] * v2[k];
-          s[k] += v3[k], q[k] += (double)v3[k] * v3[k];
-        }
-      }
-    }
-    if (MODE == 1) {
-      // two rows (six loads) in flight per thread, added in row order
-      for (; r + step < M; r += 2 * step) {
-        float va[8], vb[8], xa[8], xb[8];
-        ld8(a + r * C + 8 * g, va), ld8(a + (r + step) * C + 8 * g, vb);
-        ld8(x + r * C + 8 * g, xa), ld8(x + (r + step) * C + 8 * g, xb);
-        if (ymask) {
-          float ma[8], mb[8];
-          ld8(ymask + r * C + 8 * g, ma), ld8(ymask + (r + step) * C + 8 * g, mb);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) va[k] = ma[k] > 0.f ? va[k] : 0.f, vb[k] = mb[k] > 0.f ? vb[k] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          s[k] += va[k], q[k] += (double)va[k] * ((xa[k] - mu[k]) * rs[k]);
-          s[k] += vb[k], q[k] += (double)vb[k] * ((xb[k] - mu[k]) * rs[k]);
-        }
-      }
-    }
-    for (; r < M; r += step) {
-      float v[8];
-      ld8(a + r * C + 8 * g, v);
-      if (MODE == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] += v[k], q[k] += (double)v[k] * v[k];
-      } else {
-        float xv[8];
-        ld8(x + r * C + 8 * g, xv);
-        if (ymask) {
-          float m[8];
-          ld8(ymask + r * C + 8 * g, m);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = m[k] > 0.f ? v[k] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] += v[k], q[k] += (double)v[k] * ((xv[k] - mu[k]) * rs[k]);
-      }
-    }
-  }
-  __shared__ double red[2][256][8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) red[0][tid][k] = s[k], red[1][tid][k] = q[k];
-  __syncthreads();
-  if (tid < c8) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      double sa = 0, sb = 0;
-      for (int rr = 0; rr < rows_per_pass; ++rr) sa += red[0][rr * c8 + tid][k], sb += red[1][rr * c8 + tid][k];
-      part[(size_t)blockIdx.x * 1024 + 8 * tid + k] = sa;
-      part[(size_t)blockIdx.x * 1024 + 512 + 8 * tid + k] = sb;
-    }
-  }
-}
-
-// partial sums -> sums[c], sums[512 + c] in a FIXED order (lane l of the channel's 32 adds blocks l, l + 32, ... in turn,
-// then a shuffle tree): 8 channels per workgroup; FINAL: also mean / rstd and the running statistics
-template <bool FINAL>
-__global__ __launch_bounds__(256) void bn_sum_parts_kernel(const double* __restrict__ part, int nblocks, int C,
-                                                           double* __restrict__ sums, long long M, float eps, float momentum,
-                                                           float* __restrict__ mean, float* __restrict__ rstd,
-                                                           float* __restrict__ run_mean, float* __restrict__ run_var) {
-  const int c = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
-  double a = 0, b = 0;
-  if (c < C)
-    for (int k = l; k < nblocks; k += 32) a += part[(size_t)k * 1024 + c], b += part[(size_t)k * 1024 + 512 + c];
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) a += __shfl_down(a, o, 32), b += __shfl_down(b, o, 32);
-  if (c >= C || l != 0) return;
-  sums[c] = a, sums[512 + c] = b;
-  if (FINAL) {
-    const double mu = a / (double)M;
-    double var = b / (double)M - mu * mu;
-    if (var < 0) var = 0;
-    mean[c] = (float)mu;
-    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (run_mean) {
-      const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-      run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mu);
-      run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
-    }
-  }
-}
-
-// y = (x - mean) * rstd * gamma + beta (+ resid) (ReLU), fp16 -> fp16.  The grid stride (a multiple of 2048 elements) is a
-// multiple of C, so a thread meets the same 8 channels in every iteration: their constants are loaded once.
-__global__ __launch_bounds__(256) void bn_apply_h_kernel(const h16* __restrict__ x, const h16* __restrict__ resid,
-                                                         h16* __restrict__ y, long long n8, int C, const float* __restrict__ mean,
-                                                         const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, int relu) {
-  const int c = (threadIdx.x * 8) % C;
-  float mu[8], sc[8], be[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) mu[k] = mean[c + k], sc[k] = rstd[c + k], be[k] = beta[c + k];
-  float ga[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) ga[k] = gamma[c + k];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    float v[8], o[8];
-    ld8(x + i * 8, v);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = (v[k] - mu[k]) * sc[k] * ga[k] + be[k];
-    if (resid) {
-      float r[8];
-      ld8(resid + i * 8, r);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] += r[k];
-    }
-    if (relu) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = fmaxf(o[k], 0.f);
-    }
-    st8(y + i * 8, o);
-  }
-}
-
-// BN backward, pass 2: dx = gamma * rstd * (dy - sum_dy / M - xhat * sum_dy_xhat / M); d gamma, d beta (fp32 gradients)
-__global__ __launch_bounds__(256) void bn_bwd_apply_h_kernel(const h16* __restrict__ dy, const h16* __restrict__ x,
-                                                             const h16* __restrict__ ymask, h16* __restrict__ dx, long long n8,
-                                                             long long M, int C, const float* __restrict__ mean,
-                                                             const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                             const double* __restrict__ sums, float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta, int accumulate) {
-  if (blockIdx.x == 0) {
-    for (int c = threadIdx.x; c < C; c += 256) {
-      const float dg = (float)sums[512 + c], db = (float)sums[c];
-      dgamma[c] = accumulate ? dgamma[c] + dg : dg;
-      dbeta[c] = accumulate ? dbeta[c] + db : db;
-    }
-  }
-  const double invM = 1.0 / (double)M;
-  const int c = (threadIdx.x * 8) % C;  // the same 8 channels in every iteration (grid stride is a multiple of C)
-  float mu[8], rs[8], gr[8], sb[8], sg[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    mu[k] = mean[c + k], rs[k] = rstd[c + k], gr[k] = gamma[c + k] * rstd[c + k];
-    sb[k] = (float)(sums[c + k] * invM), sg[k] = (float)(sums[512 + c + k] * invM);
-  }
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    float d[8], v[8], o[8];
-    ld8(dy + i * 8, d);
-    ld8(x + i * 8, v);
-    if (ymask) {
-      float m[8];
-      ld8(ymask + i * 8, m);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) d[k] = m[k] > 0.f ? d[k] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = gr[k] * (d[k] - sb[k] - (v[k] - mu[k]) * rs[k] * sg[k]);
-    st8(dx + i * 8, o);
-  }
-}
-
-// out = (a + b) masked by (y > 0); b / y optional
-__global__ __launch_bounds__(256) void add_mask_h_kernel(const h16* __restrict__ a, const h16* __restrict__ b,
-                                                         const h16* __restrict__ y, h16* __restrict__ out, long long n8) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    float v[8];
-    ld8(a + i * 8, v);
-    if (b) {
-      float w[8];
-      ld8(b + i * 8, w);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] += w[k];
-    }
-    if (y) {
-      float m[8];
-      ld8(y + i * 8, m);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = m[k] > 0.f ? v[k] : 0.f;
-    }
-    st8(out + i * 8, v);
-  }
-}
-
-// 3x3/2 max-pool, pad 1, with the arg-max kept (first maximum in (dy, dx) scan order, as torch); 8 channels per thread
-__global__ __launch_bounds__(256) void maxpool_idx_h_kernel(const h16* __restrict__ in, h16* __restrict__ out,
-                                                            unsigned char* __restrict__ idx, long long total8) {
-  constexpr int HI = 112, HO = 56, C = 64;
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= total8) return;
-  const int c8 = (int)(gid % (C / 8));
-  long long p = gid / (C / 8);
-  const int ow = (int)(p % HO);
-  p /= HO;
-  const int oh = (int)(p % HO);
-  const long long b = p / HO;
-  float best[8];
-  int bi[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) best[k] = -INFINITY, bi[k] = 9;
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy) {
-    const int ih = oh * 2 - 1 + dy;
-    if ((unsigned)ih >= (unsigned)HI) continue;
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int iw = ow * 2 - 1 + dx;
-      if ((unsigned)iw >= (unsigned)HI) continue;
-      float v[8];
-      ld8(in + ((b * HI + ih) * HI + iw) * C + 8 * c8, v);
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (v[k] > best[k] || bi[k] == 9) best[k] = v[k], bi[k] = dy * 3 + dx;
-    }
-  }
-  st8(out + gid * 8, best);
-  unsigned lo = 0, hi = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) lo |= (unsigned)bi[k] << (8 * k), hi |= (unsigned)bi[4 + k] << (8 * k);
-  *reinterpret_cast<u32x2*>(idx + gid * 8) = u32x2{lo, hi};
-}
-
-// max-pool backward (gather form): every input position sums the gradients of the <= 4 windows that chose it.  A thread owns a
-// 2 x 2 quad of input positions (2y .. 2y+1, 2x .. 2x+1) x 8 channels: the quad only ever belongs to the four windows
-// (y .. y+1) x (x .. x+1) -- row 2y to window row y alone (dy = 1), row 2y+1 to window rows y (dy = 2) and y+1 (dy = 0) -- so four
-// window loads serve four outputs (one thread per position loaded nine for four)
-__global__ __launch_bounds__(256) void maxpool_bwd_h_kernel(const h16* __restrict__ dout, const unsigned char* __restrict__ idx,
-                                                            h16* __restrict__ din, long long total8) {
-  constexpr int HI = 112, HO = 56, C = 64;
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;  // (b, y, x, c8) over the 56 x 56 quads
-  if (gid >= total8) return;
-  const int c8 = (int)(gid % (C / 8));
-  long long p = gid / (C / 8);
-  const int x = (int)(p % HO);
-  p /= HO;
-  const int y = (int)(p % HO);
-  const long long b = p / HO;
-  float acc[2][2][8];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) acc[i][j][k] = 0.f;
-#pragma unroll
-  for (int wy = 0; wy < 2; ++wy) {
-    const int oh = y + wy;
-    if (oh >= HO) continue;
-#pragma unroll
-    for (int wx = 0; wx < 2; ++wx) {
-      const int ow = x + wx;
-      if (ow >= HO) continue;
-      const long long o = ((b * HO + oh) * HO + ow) * C + 8 * c8;
-      const u32x2 ib = *reinterpret_cast<const u32x2*>(idx + o);
-      float g[8];
-      ld8(dout + o, g);
-      // window (oh, ow) covers input rows 2 oh - 1 + dy: quad row i = 0 (input row 2y) is dy = 1 of wy = 0; quad row i = 1
-      // (input row 2y + 1) is dy = 2 of wy = 0 and dy = 0 of wy = 1 -- the same in x
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int dy = wy == 0 ? 1 + i : (i == 1 ? 0 : -1);
-        if (dy < 0) continue;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int dx = wx == 0 ? 1 + j : (j == 1 ? 0 : -1);
-          if (dx < 0) continue;
-          const int code = dy * 3 + dx;
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            if ((int)(((k < 4 ? ib[0] : ib[1]) >> (8 * (k & 3))) & 0xffu) == code) acc[i][j][k] += g[k];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      st8(din + (((b * HI + 2 * y + i) * HI + 2 * x + j) * C + 8 * c8), acc[i][j]);
-}
-
-__global__ __launch_bounds__(256) void avgpool_h_kernel(const h16* __restrict__ last, float* __restrict__ feats, int n) {
-  const int b = blockIdx.x, t = threadIdx.x;
-  float s0 = 0.f, s1 = 0.f;
-  for (int p = 0; p < 49; ++p) {
-    const f16x2 v = *reinterpret_cast<const f16x2*>(last + ((size_t)b * 49 + p) * 512 + 2 * t);
-    s0 += (float)v[0], s1 += (float)v[1];
-  }
-  *reinterpret_cast<float2*>(feats + (size_t)b * 512 + 2 * t) = make_float2(s0 / 49.0f, s1 / 49.0f);
-}
-
-__global__ __launch_bounds__(256) void avgpool_bwd_h_kernel(const float* __restrict__ dfeats, const h16* __restrict__ last,
-                                                            h16* __restrict__ dlast, long long total) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= total) return;
-  const int c = (int)(gid % 512);
-  const long long b = gid / (49 * 512);
-  dlast[gid] = (float)last[gid] > 0.f ? (h16)(dfeats[b * 512 + c] * (1.0f / 49.0f)) : (h16)0.f;
-}
 
 // ---------------------------------------------------------------------------------------------
 // weight gradient on the fp16 MFMA:  part[slice][tap][co][ci] = sum over the slice's output pixels m of
@@ -568,35 +163,6 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const h16* __restrict__ 
   }
 }
 
-// split-K partials -> the PyTorch-layout gradient (accumulate or overwrite).  32 weights per workgroup x 8 slice groups:
-// group g adds slices g, g + 8, ... in turn, then the 8 group sums are added in order -- a fixed order, hence deterministic
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int slices, float* __restrict__ dw,
-                                                           int cout, int cin, int ks, int stem, int accumulate) {
-  __shared__ float red[8][32];
-  const int e = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const long long gid = (long long)blockIdx.x * 32 + e;
-  const long long total = (long long)cout * cin * ks * ks;
-  float s = 0.f;
-  if (gid < total) {
-    const int kw = (int)(gid % ks);
-    long long t = gid / ks;
-    const int kh = (int)(t % ks);
-    t /= ks;
-    const int ci = (int)(t % cin), co = (int)(t / cin);
-    const size_t per_slice = stem ? (size_t)7 * cout * 32 : (size_t)total;
-    const size_t o = stem ? ((size_t)kh * cout + co) * 32 + kw * 4 + ci : ((size_t)(kh * ks + kw) * cout + co) * cin + ci;
-    for (int k = g; k < slices; k += 8) s += part[(size_t)k * per_slice + o];
-  }
-  red[g][e] = s;
-  __syncthreads();
-  if (g == 0 && gid < total) {
-    float v = red[0][e];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) v += red[k][e];
-    dw[gid] = accumulate ? dw[gid] + v : v;
-  }
-}
-
 // grads *= inv_scale; flag[0] = 1 when a gradient is not finite (GradScaler.unscale_)
 __global__ __launch_bounds__(256) void unscale_check_kernel(float* __restrict__ g, long long n, float inv_scale,
                                                             int* __restrict__ flag) {
@@ -610,89 +176,24 @@ __global__ __launch_bounds__(256) void unscale_check_kernel(float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// launch helpers
-// ---------------------------------------------------------------------------------------------
 // the fp16 precision of the shared driver (train_common.h)
+// ---------------------------------------------------------------------------------------------
+constexpr size_t kWgPartBytes = (size_t)160 << 20;
+
 struct Fp16Step {
   using T = h16;
   static constexpr const char* kName = "train_amp";
   static constexpr int kMaxBatch = 2048;  // 32-bit byte offsets
   static constexpr int kPrec = HIPAC_PREC_FP16;
-  static constexpr auto pack_w = pack_w_h_kernel;
-  static TrainPlan plan(int B) { return make_amp_plan(B); }
-  static int bn_forward(const TrainCtx& c, int i, int n, const h16* resid, int relu);
-  static int bn_backward(const TrainCtx& c, int i, int n, const h16* dy, const h16* ymask, h16* dx, float* grads, int accumulate);
+  static constexpr bool kZeroPage = true;
+  static size_t wpack_offset(int i) {
+    size_t o = 0;
+    for (int k = 0; k < i; ++k) o += (packed_w_floats(k) + 127) & ~(size_t)127;  // 256-byte aligned rows of the table
+    return o;
+  }
+  static size_t wgrad_part_bytes(int) { return kWgPartBytes; }  // conv_wgrad bounds its slices by it
   static int conv_wgrad(const TrainCtx& c, int i, int n, const h16* X, const h16* dY, float* grads, int accumulate);
-  // 8 channels per thread; the pool's backward: a 2 x 2 quad of input positions x 8 channels per thread
-  static void maxpool(const h16* in, h16* out, unsigned char* idx, int n, hipStream_t s) {
-    const long long total = (long long)n * 56 * 56 * 8;
-    hipLaunchKernelGGL(maxpool_idx_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, idx, total);
-  }
-  static void maxpool_bwd(const h16* dout, const unsigned char* idx, h16* din, int n, hipStream_t s) {
-    const long long total = (long long)n * 56 * 56 * 8;
-    hipLaunchKernelGGL(maxpool_bwd_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dout, idx, din, total);
-  }
-  static void avgpool(const h16* last, float* feats, int n, hipStream_t s) {
-    hipLaunchKernelGGL(avgpool_h_kernel, dim3(n), dim3(256), 0, s, last, feats, n);
-  }
-  static void avgpool_bwd(const float* dfeats, const h16* last, h16* dlast, int n, hipStream_t s) {
-    const long long total = (long long)n * 49 * 512;
-    hipLaunchKernelGGL(avgpool_bwd_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dfeats, last, dlast, total);
-  }
-  static void add_mask(const h16* a, const h16* b, const h16* y, h16* out, long long n_elems, hipStream_t s) {
-    const long long n8 = n_elems / 8;
-    hipLaunchKernelGGL(add_mask_h_kernel, dim3(grid_for(n8)), dim3(256), 0, s, a, b, y, out, n8);
-  }
 };
-
-static int red_blocks(long long M, int C) {
-  const int rows_per_pass = 256 / (C / 8);
-  long long gs = (M + rows_per_pass - 1) / rows_per_pass;
-  return (int)(gs > kRedBlocks ? kRedBlocks : gs);
-}
-
-int Fp16Step::bn_forward(const TrainCtx& c, int i, int n, const h16* resid, int relu) {
-  const ConvDesc& d = kConvs[i];
-  const long long M = (long long)n * d.hout * d.hout;
-  const h16* x = (const h16*)(c.ws + c.p->pre[i]);
-  h16* y = (h16*)(c.ws + c.p->post[i]);
-  double* part = (double*)(c.ws + c.p->red);
-  double* sums = (double*)(c.ws + c.p->sums);
-  float* mean = (float*)(c.ws + c.p->mean_rstd) + stat_offset(i);
-  float* rstd = mean + d.cout;
-  const float* gamma = c.params + param_offset(i) + conv_w_floats(i);
-  const int gs = red_blocks(M, d.cout);
-  hipLaunchKernelGGL((bn_reduce_h_kernel<0>), dim3(gs), dim3(256), 0, c.s, x, (const h16*)nullptr, (const h16*)nullptr, M, d.cout,
-                     (const float*)nullptr, (const float*)nullptr, part);
-  float* rm = c.stats ? c.stats + stat_offset(i) : nullptr;
-  hipLaunchKernelGGL((bn_sum_parts_kernel<true>), dim3((d.cout + 7) / 8), dim3(256), 0, c.s, (const double*)part, gs, d.cout,
-                     sums, M, c.eps, c.momentum, mean, rstd, rm, rm ? rm + d.cout : nullptr);
-  const long long n8 = M * d.cout / 8;
-  hipLaunchKernelGGL(bn_apply_h_kernel, dim3(grid_for(n8)), dim3(256), 0, c.s, x, resid, y, n8, d.cout, (const float*)mean,
-                     (const float*)rstd, gamma, gamma + d.cout, relu);
-  return (int)hipGetLastError();
-}
-
-int Fp16Step::bn_backward(const TrainCtx& c, int i, int n, const h16* dy, const h16* ymask, h16* dx, float* grads,
-                          int accumulate) {
-  const ConvDesc& d = kConvs[i];
-  const long long M = (long long)n * d.hout * d.hout;
-  const h16* x = (const h16*)(c.ws + c.p->pre[i]);
-  double* part = (double*)(c.ws + c.p->red);
-  double* sums = (double*)(c.ws + c.p->sums);
-  const float* mean = (const float*)(c.ws + c.p->mean_rstd) + stat_offset(i);
-  const float* rstd = mean + d.cout;
-  const float* gamma = c.params + param_offset(i) + conv_w_floats(i);
-  float* dgamma = grads + param_offset(i) + conv_w_floats(i);
-  const int gs = red_blocks(M, d.cout);
-  hipLaunchKernelGGL((bn_reduce_h_kernel<1>), dim3(gs), dim3(256), 0, c.s, dy, x, ymask, M, d.cout, mean, rstd, part);
-  hipLaunchKernelGGL((bn_sum_parts_kernel<false>), dim3((d.cout + 7) / 8), dim3(256), 0, c.s, (const double*)part, gs, d.cout,
-                     sums, M, 0.f, 0.f, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-  const long long n8 = M * d.cout / 8;
-  hipLaunchKernelGGL(bn_bwd_apply_h_kernel, dim3(grid_for(n8)), dim3(256), 0, c.s, dy, x, ymask, dx, n8, M, d.cout, mean, rstd,
-                     gamma, (const double*)sums, dgamma, dgamma + d.cout, accumulate);
-  return (int)hipGetLastError();
-}
 
 // weight gradient of conv i: X = the conv's input map, dY = gradient wrt its output -> grads (PyTorch layout)
 int Fp16Step::conv_wgrad(const TrainCtx& c, int i, int n, const h16* X, const h16* dY, float* grads, int accumulate) {
@@ -726,7 +227,7 @@ int Fp16Step::conv_wgrad(const TrainCtx& c, int i, int n, const h16* X, const h1
   else HIPAC_WG(64, 1, false);
 #undef HIPAC_WG
   const long long total = (long long)conv_w_floats(i);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, c.s, (const float*)part, (int)slices,
+  hipLaunchKernelGGL(wgrad_reduce_kernel<0>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, c.s, (const float*)part, (int)slices,
                      grads + param_offset(i), d.cout, d.cin, d.ks, stem ? 1 : 0, accumulate);
   return (int)hipGetLastError();
 }
@@ -737,7 +238,7 @@ using namespace hipac;
 
 extern "C" {
 
-size_t hipac_train_amp_workspace_bytes(int batch) { return batch > 0 ? make_amp_plan(batch).total : 0; }
+size_t hipac_train_amp_workspace_bytes(int batch) { return batch > 0 ? make_train_plan<Fp16Step>(batch).total : 0; }
 
 // Test tap, as hipac_train_debug_offset but for the fp16 workspace (maps are fp16 NHWC)
 int64_t hipac_train_amp_debug_offset(int batch, int kind, int conv) { return train_debug_offset<Fp16Step>(batch, kind, conv); }
