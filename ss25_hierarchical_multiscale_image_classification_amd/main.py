@@ -17,8 +17,17 @@ tree), ``--precision {bf16,fp16,fp16x3,fp16q8,fp32}``, ``--weights PATH``, ``--s
 nn.DataParallel, src/main.py:481-482, :841-842: ``--patch`` / ``--extract_features`` shard the
 slides, ``--train*`` the batches; started by this program itself before it touches a GPU).
 
-``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by
-``features.save_froc_csv``) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
+``--detect`` writes those detection lists (``detect.py``): every slide in ``<data_root>/test/img`` (and every
+``--synthetic`` spec) is scanned densely with the two-class network of ``--weights`` at the levels of ``--patch_level``
+(``all`` = levels 0-3 fused cell by cell), and the tumour probability map, its Gaussian smoothing and the non-maximum
+suppression run on the device; one ``probability,x,y`` line per detection goes to
+``./models/first_model/model_predictions_csv/<case>.csv`` (``--detect_save_maps``: the fused map to
+``./models/first_model/heatmaps/<case>.npy``).  ``--detect_cell`` / ``--detect_fuse`` / ``--detect_sigma`` /
+``--detect_radius`` / ``--detect_threshold`` / ``--detect_max`` set the post-processing; under ``--world_size N`` the slides
+are sharded.  ``--detect --run_evaluation`` detects first, then scores.
+
+``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by ``--detect``, or by
+``features.save_froc_csv`` with one line per window) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
 
 ``--train_mil`` trains the ABMIL slide classifier (``mil_train.py``, the loop of the reference's
@@ -107,6 +116,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mil_bag_size", type=int, default=None, help="sample at most this many patches per bag and epoch (default: the whole bag)")
     p.add_argument("--mil_bags_per_step", type=int, default=32)
     p.add_argument("--mil_model", type=str, default=os.path.join("models", "mil_model.pth"))
+    p.add_argument("--detect", action="store_true",
+                   help="write the detection CSVs --run_evaluation scores: dense scan of <data_root>/test/img at the levels of "
+                        "--patch_level, probability map, smoothing and NMS on the device")
+    p.add_argument("--detect_cell", type=int, default=224, help="cell of the probability map in level-0 pixels (divides 1792)")
+    p.add_argument("--detect_fuse", choices=["mean", "max"], default="mean", help="how the levels' maps are combined per cell")
+    p.add_argument("--detect_sigma", type=float, default=1.0, help="Gaussian smoothing of the fused map, in cells (0 = none)")
+    p.add_argument("--detect_radius", type=int, default=4, help="NMS radius in cells")
+    p.add_argument("--detect_threshold", type=float, default=0.5, help="smallest probability of a detection")
+    p.add_argument("--detect_max", type=int, default=2000, help="most detections per slide")
+    p.add_argument("--detect_save_maps", action="store_true", help="also write models/first_model/heatmaps/<case>.npy (float32[gh][gw])")
     p.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)
     return p
 
@@ -119,9 +138,10 @@ def levels_of(args) -> List[int]:
     return [0, 1, 2, 3] if args.patch_level == "all" else [int(args.patch_level)]
 
 
-def list_slides(args):
-    """[(name, opener)] of every slide in processing order -- synthetic specs first, then the files in train/img --
-    without loading any: ``opener()`` puts the slide into HBM (a rank opens only the slides it owns)."""
+def list_slides(args, split: str = "train"):
+    """[(name, opener)] of every slide in processing order -- synthetic specs first, then the files in <split>/img --
+    without loading any: ``opener()`` puts the slide into HBM (a rank opens only the slides it owns).  The annotations of
+    <split>/mask/annotations are attached where they exist (they label the windows; detection does not read the labels)."""
     from .extract import DeviceSlide, parse_annotation_xml
 
     out = []
@@ -130,10 +150,10 @@ def list_slides(args):
         w, h, seed = int(parts[0]), int(parts[1]), int(parts[2])
         name = parts[3] if len(parts) > 3 else f"synthetic_{seed}"
         out.append((name, lambda w=w, h=h, seed=seed, name=name: DeviceSlide.synthetic(w, h, seed=seed, name=name)))
-    img_dir = os.path.join(data_root(args), "train", "img")
+    img_dir = os.path.join(data_root(args), split, "img")
     if not os.path.isdir(img_dir):
         return out
-    ann_dir = os.path.join(data_root(args), "train", "mask", "annotations")
+    ann_dir = os.path.join(data_root(args), split, "mask", "annotations")
 
     def open_file(path, stem, ext):
         if ext == ".npz":
@@ -292,6 +312,52 @@ def cmd_train(args, strategy: Optional[str]):
     return 0
 
 
+def detect_geometry(args):
+    """The checked geometry and parameters of --detect, or None after a message (no GPU is touched)."""
+    from . import detect
+
+    try:
+        geom = detect.geometry(args.detect_cell, levels_of(args))
+        detect.check_parameters(args.detect_sigma, args.detect_radius, args.detect_max, args.detect_fuse)
+    except ValueError as e:
+        print(f"[ERROR] --detect: {e}")
+        return None
+    return geom
+
+
+def cmd_detect(args):
+    from . import detect
+    from .dist import rank_world, shard_units
+
+    geom = detect_geometry(args)
+    if geom is None:
+        return 2
+    slides = list_slides(args, split="test")
+    if not slides:
+        print(f"[ERROR] No slides to detect on: '{os.path.join(data_root(args), 'test', 'img')}' holds none and no --synthetic was given.")
+        return 1
+    net = load_net(args, num_classes=2)
+    csv_dir = os.path.join(os.getcwd(), "models", "first_model", "model_predictions_csv")
+    map_dir = os.path.join(os.getcwd(), "models", "first_model", "heatmaps")
+    os.makedirs(csv_dir, exist_ok=True)
+    if args.detect_save_maps:
+        os.makedirs(map_dir, exist_ok=True)
+    rank, world = rank_world()  # N > 1: every rank detects on the slides it owns and writes their files
+    for i in shard_units(len(slides), rank, world):
+        name = slides[i][0]
+        slide = try_open(name, slides[i][1])
+        if slide is None:
+            continue
+        res = detect.detect_slide(slide, net, levels=geom.levels, cell=geom.cell, fuse=args.detect_fuse, sigma=args.detect_sigma,
+                                  radius=args.detect_radius, threshold=args.detect_threshold, max_detections=args.detect_max)
+        n = detect.save_detection_csv(os.path.join(csv_dir, name + ".csv"), res)
+        if args.detect_save_maps:
+            np.save(os.path.join(map_dir, name + ".npy"), res.fused.cpu().numpy())
+        print(f"[INFO] {name}: {res.probs.shape[0]} windows at levels {list(geom.levels)}, map {res.grid[0]} x {res.grid[1]} cells of "
+              f"{geom.cell} px, {n} detections", flush=True)
+    return 0
+
+
 def cmd_run_evaluation(args):
     from .dist import rank_world
     from .froc import run_evaluation
@@ -356,6 +422,8 @@ def main(argv=None) -> int:
     if (args.train_mil or args.predict_mil) and args.patch_level == "all":
         mil_triple(args)  # prints why; refused before any process is started or any GPU touched
         return 2
+    if args.detect and detect_geometry(args) is None:  # refused before any process is started or any GPU touched
+        return 2
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.world_size > 1 and not under_launcher:
         # parent: start one fresh process per GPU and supervise them; nothing here may initialise the GPU
@@ -403,6 +471,9 @@ def _dispatch(args) -> int:
         rc = cmd_train(args, None) or rc
     if args.train_strategy:
         rc = cmd_train(args, args.strategy) or rc
+    if args.detect:
+        rc = cmd_detect(args) or rc
+        _rendezvous()  # --run_evaluation on rank 0 reads every rank's CSVs
     if args.run_evaluation:
         rc = cmd_run_evaluation(args) or rc
     if args.train_mil:
