@@ -144,6 +144,19 @@ _lib = None
 _lock = threading.Lock()
 
 
+def bind_symbols(lib, symbols, version_symbol: str, version: int, what: str):
+    """Set restype / argtypes of every entry of ``symbols`` (name -> (restype, argtypes)) on ``lib`` and check the
+    version ``version_symbol`` reports against the binding's ``version``.  ``what`` names the ABI in the error."""
+    for name, (res, args) in symbols.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    got = getattr(lib, version_symbol)()
+    if got != version:
+        raise HipacError(f"{what} version mismatch: library {got}, binding {version}")
+    return lib
+
+
 def load_library(path: Optional[os.PathLike] = None):
     """dlopen the library and bind every symbol.  Raises HipacError if absent."""
     global _lib
@@ -157,12 +170,7 @@ def load_library(path: Optional[os.PathLike] = None):
                 "(there is no CPU fallback for the HIP path)"
             )
         lib = C.CDLL(str(p))
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.hipac_abi_version() != ABI_VERSION:
-            raise HipacError(f"ABI version mismatch: library {lib.hipac_abi_version()}, binding {ABI_VERSION}")
+        bind_symbols(lib, SYMBOLS, "hipac_abi_version", ABI_VERSION, "ABI")
         if path is None:
             _lib = lib
         return lib

@@ -63,6 +63,9 @@ template <> struct Elem<float> {
   }
 };
 
+// Workspace offsets and sizes are multiples of 256 bytes.
+static inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // Fixed ResNet18@224 geometry.
 constexpr int kPatch = HIPAC_PATCH;
 constexpr int kPadH = HIPAC_PAD_H;
@@ -89,7 +92,7 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 // precision fp16q8 (halo16x2.h): the constant power-of-two scales of the e4m3 byte planes.  Activations: hi8 = e4m3(hi), lo8 = e4m3(lo * 2^11);
-// weights (pack_conv_q8): whi8 = e4m3(whi * 2^4), wlo8 = e4m3(wlo * 2^15).  Both cross products carry 2^(11 + 4) = 2^(0 + 15).
+// weights (resnet_pack.hip, pack_conv_pairs): whi8 = e4m3(whi * 2^4), wlo8 = e4m3(wlo * 2^15).  Both cross products carry 2^(11 + 4) = 2^(0 + 15).
 constexpr int kQ8LoShift = 11, kQ8WhiShift = 4, kQ8WloShift = 15;
 static_assert(kQ8LoShift + kQ8WhiShift == kQ8WloShift, "one scale for both cross products");
 
@@ -148,7 +151,8 @@ Plan make_plan(int batch, int precision = 0);
 constexpr int kNumOps = 21;
 constexpr int kNumEarlyOps = 11;  // stem, pool, layer1 (4), layer2 (5)
 
-// per-precision launchers (conv_bf16.hip / conv_f16.hip): ops first..last of the trunk.
+// per-precision launchers (conv_bf16.hip, conv_f16.hip, conv_f32.hip, conv_f16x3.hip, conv_f16q8.hip: one instantiation of
+// trunk.h each): ops first..last of the trunk.
 // Early ops run on `n_early` images (one sub-batch, whose layer2 output lands at image
 // offset `img_off` of the group buffer); late ops on `n_late` images (one group).
 int run_trunk_bf16(const Net& net, const Plan& p, char* ws, const void* xin, int n_early, int img_off, int n_late,
@@ -167,7 +171,7 @@ int launch_u8_to_nhwc4_f32(const unsigned char* x, const float* lut, float* out,
 int launch_gemm_f32(const float* a, long long sam, long long sak, const float* b, long long sbn, long long sbk, float* c, long long ldc,
                     int M, int N, int K, hipStream_t s);
 
-// elementwise.hip
+// resnet_head.hip
 int launch_nchw_to_nhwc4(const float* x, void* out, int n, int precision, hipStream_t s);
 int launch_head(const float* last, int n, const float* fc_w, const float* fc_b, int num_classes,
                 float* feats, float* logits, int64_t* labels, hipStream_t s);

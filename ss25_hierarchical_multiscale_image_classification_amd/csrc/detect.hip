@@ -226,8 +226,6 @@ __global__ __launch_bounds__(256) void nms_emit_kernel(const uint64_t* __restric
   if (k + 1 == M || keys[k + 1] == kNmsNoKey) *count = k + 1;
 }
 
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static bool grid_ok(int gw, int gh) { return gw >= 1 && gh >= 1 && (int64_t)gw * gh < ((int64_t)1 << 31); }
 
 static size_t pow2_at_least(size_t n) {

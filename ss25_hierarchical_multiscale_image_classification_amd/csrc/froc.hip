@@ -293,8 +293,6 @@ __global__ __launch_bounds__(256) void eval_lookup_kernel(const int32_t* __restr
   out[i] = (x >= 0 && x < W && y >= 0 && y < H) ? labels[y * W + x] : 0;
 }
 
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static bool eval_size_ok(int W, int H) { return W >= 1 && H >= 1 && (int64_t)W * H < ((int64_t)1 << 31); }
 
 }  // namespace hipac

@@ -118,7 +118,7 @@ __host__ __device__ constexpr int perm16_inv(int j) { return (j & 1) ? (j + 7) /
 // slot r of M-tile mt = image (mt * BM) / (H*W) + r.  Per lane the eight
 // pixels are summed in order into the accumulator set of the sub-tile's first image (A) or of the next one (B; a 16-pixel
 // sub-tile meets at most two images), a set is reduced over the 16 lanes of a row (four DPP rotations) and written when the
-// walk leaves its image: no atomics, one fixed order, so the features are reproducible bit for bit.  hipac_capi.hip's
+// walk leaves its image: no atomics, one fixed order, so the features are reproducible bit for bit.  resnet_head.hip's
 // head_pool_kernel adds the <= 2 x WM partial sums of an image in a fixed order, divides by H*W and applies the fc.
 constexpr int kPoolSlots = 7;  // images a 256-pixel tile of 49-pixel maps can meet (1 + 5 x 49 + 10)
 

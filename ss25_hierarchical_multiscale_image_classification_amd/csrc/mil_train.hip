@@ -55,7 +55,7 @@ static MilTrainPlan make_mil_train_plan(const hipac_mil_params_t* p, int pooling
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
-    o += (bytes + 255) / 256 * 256;
+    o += align256(bytes);
     return at;
   };
   q.bag_of = take((size_t)n * 4);

@@ -82,7 +82,7 @@ static TrainPlan make_train_plan(int B) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
+    off += align256(bytes);
     return o;
   };
   const size_t b = (size_t)B;

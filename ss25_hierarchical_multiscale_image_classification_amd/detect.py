@@ -50,13 +50,7 @@ def load_detect_library():
     global _bound
     lib = capi.load_library()
     if _bound is not lib:
-        for name, (res, args) in DETECT_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.hipac_detect_abi_version() != DETECT_ABI_VERSION:
-            raise capi.HipacError(f"detect ABI version mismatch: library {lib.hipac_detect_abi_version()}, binding {DETECT_ABI_VERSION}")
-        _bound = lib
+        _bound = capi.bind_symbols(lib, DETECT_SYMBOLS, "hipac_detect_abi_version", DETECT_ABI_VERSION, "detect ABI")
     return lib
 
 

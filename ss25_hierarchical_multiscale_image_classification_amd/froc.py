@@ -51,13 +51,7 @@ def load_eval_library():
     global _bound
     lib = capi.load_library()
     if _bound is not lib:
-        for name, (res, args) in EVAL_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.hipac_eval_abi_version() != EVAL_ABI_VERSION:
-            raise capi.HipacError(f"eval ABI version mismatch: library {lib.hipac_eval_abi_version()}, binding {EVAL_ABI_VERSION}")
-        _bound = lib
+        _bound = capi.bind_symbols(lib, EVAL_SYMBOLS, "hipac_eval_abi_version", EVAL_ABI_VERSION, "eval ABI")
     return lib
 
 

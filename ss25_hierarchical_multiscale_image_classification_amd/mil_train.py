@@ -45,14 +45,8 @@ def load_mil_train_library():
     global _bound
     lib = capi.load_library()
     if _bound is not lib:
-        for name, (res, args) in MIL_TRAIN_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.hipac_mil_train_abi_version() != MIL_TRAIN_ABI_VERSION:
-            raise capi.HipacError(f"MIL training ABI version mismatch: library {lib.hipac_mil_train_abi_version()}, "
-                                  f"binding {MIL_TRAIN_ABI_VERSION}")
-        _bound = lib
+        _bound = capi.bind_symbols(lib, MIL_TRAIN_SYMBOLS, "hipac_mil_train_abi_version", MIL_TRAIN_ABI_VERSION,
+                                   "MIL training ABI")
     return lib
 
 

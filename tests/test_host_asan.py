@@ -53,6 +53,12 @@ DRIVER = textwrap.dedent("""
     assert lib.hipac_train_amp_encoder_forward(None, None, None, 4, 0.1, 1e-5, None, None, 0, None) != 0
     assert b"train_amp_forward: null argument" in lib.hipac_last_error()
     assert lib.hipac_adam_step(None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 1, None) != 0
+    assert lib.hipac_resnet18_pack(None, 0, None) != 0
+    assert b"pack: null argument" in lib.hipac_last_error()
+    params, handle = capi.ResNet18Params(), C.c_void_p()
+    params.num_classes = 2  # fc_w stays NULL
+    assert lib.hipac_resnet18_pack(C.byref(params), 0, C.byref(handle)) != 0 and not handle.value
+    assert b"pack: fc_w / num_classes mismatch" in lib.hipac_last_error()
     print("asan drive ok")
 """)
 
