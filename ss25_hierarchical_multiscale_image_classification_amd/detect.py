@@ -263,9 +263,11 @@ def detections_from_scores(logits, meta, level0_size: Tuple[int, int], levels: S
 
 @torch.no_grad()
 def detect_slide(slide, net, levels: Sequence[int] = (0, 1, 2, 3), cell: int = 224, fuse: str = "mean", sigma: float = 1.0,
-                 radius: int = 4, threshold: float = 0.5, max_detections: int = 2000, tumor_class: int = 1) -> DetectionResult:
+                 radius: int = 4, threshold: float = 0.5, max_detections: int = 2000, tumor_class: int = 1,
+                 tissue=None) -> DetectionResult:
     """Dense scan of ``slide`` (``extract.DeviceSlide``) with the two-class ``net`` at every level of ``levels`` and the
-    detection stage over the logits."""
+    detection stage over the logits.  ``tissue`` (``tissue.TissueFilter``, default None = the whiteness test): the windows
+    are chosen by the slide's Otsu tissue mask, one mask for all levels."""
     from .extract import score_slide
 
     geom = geometry(cell, levels)
@@ -280,7 +282,7 @@ def detect_slide(slide, net, levels: Sequence[int] = (0, 1, 2, 3), cell: int = 2
     # level is scored, so four dense levels of a large slide held at once could reach tens of GB (an estimate from the window
     # counts, not a measurement)
     for level in geom.levels:
-        _, lg, _, mt = score_slide(slide, net, levels=(level,), stride=geom.stride(level))
+        _, lg, _, mt = score_slide(slide, net, levels=(level,), stride=geom.stride(level), tissue=tissue)
         if lg is not None and mt.shape[0]:
             logits.append(lg), metas.append(mt)
     lg = torch.cat(logits) if logits else torch.empty((0, 2), dtype=torch.float32, device=dev)

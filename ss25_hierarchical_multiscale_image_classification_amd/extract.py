@@ -215,14 +215,16 @@ class LevelScan:
 
 def iter_level(slide: DeviceSlide, level: int, out_format: str = "bf16", batch_windows: int = 512,
                stride: Optional[int] = None, pad: bool = True, kept_only: bool = True,
-               use_planes: Optional[bool] = None) -> Iterator[dict]:
+               use_planes: Optional[bool] = None, tissue=None) -> Iterator[dict]:
     """Stream one level: for each batch of windows run the preprocess kernel and yield
     {"x": network input (kept windows only when ``kept_only``), "xy", "sums", "keep",
     "labels"} -- all device tensors.
 
     ``use_planes`` (default: whenever it applies, i.e. uint8 output, P > 224 and a stride that is
     a multiple of 224) resamples the level once (``capi.LevelPlanes``) and gathers windows from
-    it instead of resampling every overlapping window separately; results are identical."""
+    it instead of resampling every overlapping window separately; results are identical.
+
+    ``tissue`` (``tissue.TissueFilter``, default None = the whiteness test): "keep" is the tissue mask's decision."""
     width, height = slide.level_dimensions[level]
     P, eff_stride, xy_np = window_grid(width, height, level, stride, pad)
     img = slide.levels[level]
@@ -237,6 +239,8 @@ def iter_level(slide: DeviceSlide, level: int, out_format: str = "bf16", batch_w
         for i0 in range(0, len(xy_np), batch_windows):
             xy = torch.from_numpy(xy_np[i0 : i0 + batch_windows]).to(slide.device)
             sums, keep = planes.stats(xy)
+            if tissue is not None:
+                keep, _ = tissue.window_keep(slide, xy, level)
             labels = (capi.window_labels(mask, xy, P) if mask is not None
                       else torch.zeros((xy.shape[0],), dtype=torch.uint8, device=slide.device))
             sel = xy.index_select(0, torch.nonzero(keep, as_tuple=False).flatten()) if kept_only else xy
@@ -245,6 +249,8 @@ def iter_level(slide: DeviceSlide, level: int, out_format: str = "bf16", batch_w
     for i0 in range(0, len(xy_np), batch_windows):
         xy = torch.from_numpy(xy_np[i0 : i0 + batch_windows]).to(slide.device)
         out, sums, keep = capi.tile_preprocess(img, xy, P, out_format, width=width)
+        if tissue is not None:
+            keep, _ = tissue.window_keep(slide, xy, level)
         if mask is not None:
             labels = capi.window_labels(mask, xy, P)
         else:
@@ -255,22 +261,27 @@ def iter_level(slide: DeviceSlide, level: int, out_format: str = "bf16", batch_w
         yield {"x": out, "xy": xy, "sums": sums, "keep": keep, "labels": labels}
 
 
-def scan_level(slide: DeviceSlide, level: int, stride: Optional[int] = None, pad: bool = True, **_ignored) -> LevelScan:
+def scan_level(slide: DeviceSlide, level: int, stride: Optional[int] = None, pad: bool = True, tissue=None, **_ignored) -> LevelScan:
     """Decisions only (no pixels kept): the device-side equivalent of one
     ``extract_patches(level=...)`` pass over one slide."""
-    lw = LevelWindows(slide, level, stride=stride, pad=pad)
+    lw = LevelWindows(slide, level, stride=stride, pad=pad, tissue=tissue)
     return LevelScan(level, lw.P, lw.xy, lw.sums, lw.keep, lw.labels)
 
 
 class LevelWindows:
     """All extractor decisions of one level at once (device tensors, reference visiting
     order): window origins, whiteness sums, keep flags, tumour labels -- plus the resized
-    uint8 pixels of any subset of windows on demand."""
+    uint8 pixels of any subset of windows on demand.
+
+    ``tissue`` (``tissue.TissueFilter``; None = the reference's whiteness test): ``keep`` is the decision of the slide's Otsu
+    tissue mask, made from the mask's area table before any window pixel is touched.  On the planes path ``sums`` is still
+    what ``planes.stats`` returns; on the per-window path only the windows the mask keeps are resampled and ``sums`` is 0
+    for the others."""
 
     CHUNK = 8192  # windows per launch of the per-window kernel (non-lattice grids)
 
     def __init__(self, slide: DeviceSlide, level: int, stride: Optional[int] = None, pad: bool = True,
-                 use_planes: Optional[bool] = None):
+                 use_planes: Optional[bool] = None, tissue=None):
         self.level = level
         width, height = slide.level_dimensions[level]
         self.P, eff_stride, xy_np = window_grid(width, height, level, stride, pad)
@@ -283,8 +294,25 @@ class LevelWindows:
         if use_planes and not can_planes:
             raise capi.HipacError("planes path needs P in (448, 896, 1792) and a stride multiple of 224")
         self._kept_u8, self._kept_pos = None, None
+        tmask = tissue.mask(slide) if tissue is not None else None
         if self.planes is not None:
             self.sums, self.keep = self.planes.stats(self.xy)
+            if tmask is not None:
+                self.keep, _ = tmask.window_keep(self.xy, level, tissue.min_frac)
+        elif tmask is not None:
+            # the mask decides first; the per-window kernel then runs over the kept windows alone
+            n = self.xy.shape[0]
+            self.keep, _ = tmask.window_keep(self.xy, level, tissue.min_frac)
+            kept = torch.nonzero(self.keep, as_tuple=False).flatten()
+            kept_xy = self.xy.index_select(0, kept)
+            self.sums = torch.zeros((n,), dtype=torch.int32, device=slide.device)
+            pix = []
+            for i0 in range(0, kept.shape[0], self.CHUNK):
+                o, sm, _ = capi.tile_preprocess(self.img, kept_xy[i0:i0 + self.CHUNK].contiguous(), self.P, "u8", width=width)
+                self.sums[kept[i0:i0 + self.CHUNK]] = sm
+                pix.append(o)
+            self._kept_u8 = torch.cat(pix) if pix else torch.empty((0, 224, 224, 3), dtype=torch.uint8, device=slide.device)
+            self._kept_pos = torch.cumsum(self.keep.to(torch.int64), 0) - 1  # window index -> row of _kept_u8
         else:
             # any other window list: per-window kernel, in chunks, keeping only the pixels of kept windows (a level
             # scanned with a small stride has hundreds of thousands of windows: 150 KB each for all of them, dropped
@@ -303,6 +331,8 @@ class LevelWindows:
                 self.keep = torch.empty((0,), dtype=torch.uint8, device=slide.device)
                 self._kept_u8 = torch.empty((0, 224, 224, 3), dtype=torch.uint8, device=slide.device)
             self._kept_pos = torch.cumsum(self.keep.to(torch.int64), 0) - 1  # window index -> row of _kept_u8
+        if tmask is not None:  # for the report line; read after the slide's results are back
+            tmask.kept[level] = (self.keep.sum(dtype=torch.int64), int(self.xy.shape[0]))
         mask = slide.mask(level)
         if mask is None:
             self.labels = torch.zeros((self.xy.shape[0],), dtype=torch.uint8, device=slide.device)
@@ -336,14 +366,14 @@ class WSIPatchStream:
     ToTensor/Normalize itself), meta int32[B,4] = (level, x, y, label)."""
 
     def __init__(self, slide: DeviceSlide, levels: Sequence[int] = (0, 1, 2, 3), batch_windows: int = 4096,
-                 precision: str = "bf16", stride: Optional[int] = None):
+                 precision: str = "bf16", stride: Optional[int] = None, tissue=None):
         self.slide, self.levels, self.batch_windows = slide, tuple(levels), batch_windows
-        self.precision, self.stride = precision, stride
+        self.precision, self.stride, self.tissue = precision, stride, tissue
 
     def __iter__(self):
         for level in self.levels:
             stride = self.stride(level) if callable(self.stride) else self.stride
-            lw = LevelWindows(self.slide, level, stride)
+            lw = LevelWindows(self.slide, level, stride, tissue=self.tissue)
             kept = lw.kept_index()
             for i0 in range(0, kept.shape[0], self.batch_windows):
                 idx = kept[i0 : i0 + self.batch_windows]
@@ -352,11 +382,13 @@ class WSIPatchStream:
 
 @torch.no_grad()
 def score_slide(slide: DeviceSlide, net: capi.PackedResNet18, levels: Sequence[int] = (0, 1, 2, 3),
-                batch_windows: int = 4096, stride=None, want_logits: bool = True, fwd_batch: int = 8192):
+                batch_windows: int = 4096, stride=None, want_logits: bool = True, fwd_batch: int = 8192, tissue=None):
     """Whole-slide hierarchical scan: windows -> whiteness/labels -> resize -> ResNet18 ->
     per-patch features / logits / labels.  ``stride``: None (reference: 224), an int, or a callable level -> stride.
     Returns device tensors (feats[n,512], logits[n,C] or None, pred int64[n] or None,
     meta int32[n,4] = (level, x, y, label)) in level-major, reference visiting order.
+    ``tissue`` (``tissue.TissueFilter``, default None = the whiteness test) selects the windows with the slide's Otsu tissue
+    mask instead; its stages are queued on the same stream ahead of the decisions and add no wait of the host.
 
     Three phases on the caller's stream, ONE wait of the host per slide:
       1. the extractor's decisions for every requested level (whole-level kernels: resample planes, whiteness sums,
@@ -392,7 +424,7 @@ def score_slide(slide: DeviceSlide, net: capi.PackedResNet18, levels: Sequence[i
 
     t_dbg = _mark("start", _time.perf_counter()) if dbg else 0.0
     with trace.span("window decisions, all levels"):
-        lws = [LevelWindows(slide, lv, stride_of(lv)) for lv in levels]
+        lws = [LevelWindows(slide, lv, stride_of(lv), tissue=tissue) for lv in levels]
         # the host's one wait: the kept counts of all levels in one small copy (the index lists themselves follow at once)
         counts = torch.stack([lw.keep.sum(dtype=torch.int64) for lw in lws]).cpu().tolist() if lws else []
     n_total = int(sum(counts))
@@ -425,14 +457,14 @@ def score_slide(slide: DeviceSlide, net: capi.PackedResNet18, levels: Sequence[i
     return feats, logits, preds, metas
 
 
-def save_patch_pngs(slide: DeviceSlide, level: int, out_dir: str, stride: Optional[int] = None) -> int:
+def save_patch_pngs(slide: DeviceSlide, level: int, out_dir: str, stride: Optional[int] = None, tissue=None) -> int:
     """Optional reference-compatible output: write every kept window as
     ``<out_dir>/<slide>/<slide>_x{x}_y{y}_{label}.png`` (src/main.py:722-726).  This is
     the slow, host-bound leg (D2H copy + PNG encode) kept for downstream tools; the fused
     path never touches disk (PNG is lossless, so skipping it changes nothing)."""
     from PIL import Image
 
-    scan = scan_level(slide, level, stride=stride)
+    scan = scan_level(slide, level, stride=stride, tissue=tissue)
     P = scan.patch_size
     width, height = slide.level_dimensions[level]
     img = slide.levels[level]

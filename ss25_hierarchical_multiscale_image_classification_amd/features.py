@@ -105,11 +105,11 @@ def save_froc_csv(path: str, logits, meta, level_downsamples, tumor_class: int =
 
 @torch.no_grad()
 def extract_features_from_slide(slide: DeviceSlide, net: capi.PackedResNet18, level: int,
-                                stride: Optional[int] = None, batch_windows: int = 512):
+                                stride: Optional[int] = None, batch_windows: int = 512, tissue=None):
     """Fused equivalent for one slide and level; ``paths`` are the names the
-    reference's extractor would have written for the kept windows."""
+    reference's extractor would have written for the kept windows (``tissue``: see ``score_slide``)."""
     feats, _, _, meta = score_slide(slide, net, levels=(level,), batch_windows=batch_windows, stride=stride,
-                                    want_logits=False)
+                                    want_logits=False, tissue=tissue)
     m = meta.cpu().numpy()
     paths = [f"{slide.name}/{slide.name}_x{x}_y{y}_{LABEL_NAMES[int(l)]}.png" for _, x, y, l in m]
     return feats.cpu(), m[:, 3].astype(np.int64), paths

@@ -26,6 +26,12 @@ suppression run on the device; one ``probability,x,y`` line per detection goes t
 ``--detect_radius`` / ``--detect_threshold`` / ``--detect_max`` set the post-processing; under ``--world_size N`` the slides
 are sharded.  ``--detect --run_evaluation`` detects first, then scores.
 
+``--tissue_filter otsu`` replaces the whiteness test (``mean > 240``, the reference's rule and the default ``white``) with an
+Otsu tissue mask made on the device (``tissue.py``): a saturation threshold on a 1 : 32 thumbnail of the coarsest level, a 3 x 3
+opening, a dilation by ``--tissue_dilate`` mask pixels, never below ``--tissue_sat_floor``; a window is kept when at least
+``--tissue_min`` of its mask rectangle is tissue.  Honoured by ``--patch``, ``--extract_features`` on the fused slide route and
+``--detect``; ``--tissue_save_masks`` writes ``./models/first_model/tissue_masks/<case>.npy`` (uint8[mh][mw]).
+
 ``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by ``--detect``, or by
 ``features.save_froc_csv`` with one line per window) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
@@ -126,6 +132,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--detect_threshold", type=float, default=0.5, help="smallest probability of a detection")
     p.add_argument("--detect_max", type=int, default=2000, help="most detections per slide")
     p.add_argument("--detect_save_maps", action="store_true", help="also write models/first_model/heatmaps/<case>.npy (float32[gh][gw])")
+    p.add_argument("--tissue_filter", choices=["white", "otsu"], default="white",
+                   help="which windows are kept: white = the reference's mean > 240 test, otsu = an Otsu saturation mask of the slide")
+    p.add_argument("--tissue_min", type=float, default=0.05, help="otsu: smallest tissue fraction of a window's mask rectangle (0..1)")
+    p.add_argument("--tissue_dilate", type=int, default=1, help="otsu: radius of the mask's final dilation in mask pixels (0..8)")
+    p.add_argument("--tissue_sat_floor", type=int, default=16, help="otsu: the saturation threshold never goes below this (0..255)")
+    p.add_argument("--tissue_save_masks", action="store_true", help="otsu: also write models/first_model/tissue_masks/<case>.npy (uint8[mh][mw])")
     p.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)
     return p
 
@@ -203,10 +215,35 @@ def open_slides(args, rank: int = 0, world: int = 1):
             yield i, slide
 
 
+def tissue_filter(args):
+    """The ``tissue.TissueFilter`` of the --tissue_* flags, None for the default ``white``; ValueError for a bad value (no GPU
+    is touched)."""
+    from .tissue import TissueFilter, check_parameters
+
+    check_parameters(args.tissue_min, args.tissue_dilate, args.tissue_sat_floor)  # checked whichever filter is chosen
+    if args.tissue_filter != "otsu":
+        return None
+    return TissueFilter(min_frac=args.tissue_min, dilate=args.tissue_dilate, sat_floor=args.tissue_sat_floor, opening=True)
+
+
+def report_tissue(args, tissue, slide):
+    """The per-slide line of --tissue_filter otsu (and the mask file of --tissue_save_masks); called when the slide's results
+    are back, so reading the thresholds here costs no wait inside the scan."""
+    if tissue is None:
+        return
+    tm = tissue.mask(slide)
+    print(f"[INFO] {slide.name}: {tm.report()}", flush=True)
+    if args.tissue_save_masks:
+        mask_dir = os.path.join(os.getcwd(), "models", "first_model", "tissue_masks")
+        os.makedirs(mask_dir, exist_ok=True)
+        np.save(os.path.join(mask_dir, slide.name + ".npy"), tm.mask.cpu().numpy())
+
+
 def cmd_patch(args):
     from .dist import rank_world
     from .extract import save_patch_pngs, scan_level
 
+    tissue = tissue_filter(args)
     rank, world = rank_world()  # N > 1: every rank extracts the slides it owns; the outputs are per-slide directories
     for _, slide in open_slides(args, rank, world):
         for level in levels_of(args):
@@ -216,14 +253,15 @@ def cmd_patch(args):
                 print(f"[INFO] Patches for {slide.name} already extracted, skipping.")
                 continue
             os.makedirs(save_dir, exist_ok=True)
-            scan = scan_level(slide, level, stride=args.stride)
+            scan = scan_level(slide, level, stride=args.stride, tissue=tissue)
             np.savez(os.path.join(save_dir, "manifest.npz"), xy=scan.xy.cpu().numpy(),
                      keep=scan.keep.cpu().numpy(), labels=scan.labels.cpu().numpy(),
                      sums=scan.sums.cpu().numpy().astype(np.uint32), patch_size=scan.patch_size, level=level)
             n = int(scan.keep.sum().item())
             if args.write_png:
-                save_patch_pngs(slide, level, level_dir, stride=args.stride)
+                save_patch_pngs(slide, level, level_dir, stride=args.stride, tissue=tissue)
             print(f"[INFO] Patch extraction complete for {slide.name} at level {level}. Total patches: {n}")
+        report_tissue(args, tissue, slide)
 
 
 def load_net(args, num_classes: Optional[int] = None):
@@ -255,7 +293,10 @@ def cmd_extract_features(args):
     from .extract import score_slide
 
     rank, world = rank_world()
+    tissue = tissue_filter(args)
     if has_png:
+        if tissue is not None and rank == 0:
+            print("[INFO] --tissue_filter otsu does not apply to a PNG patch tree: its patches were chosen when they were extracted")
         if world > 1 and rank == 0:
             print("[INFO] PNG patch tree: scored by rank 0 (the fused slide path is the one that shards)")
         if rank != 0:
@@ -275,7 +316,8 @@ def cmd_extract_features(args):
                 dev = torch.device("cuda", torch.cuda.current_device())
                 return torch.zeros((0, 512), dtype=torch.float32, device=dev), None, torch.zeros((0, 4), dtype=torch.int32, device=dev)
             f, _, _, meta = score_slide(slide, net, levels=(level,), batch_windows=512, stride=args.stride,
-                                        want_logits=False)
+                                        want_logits=False, tissue=tissue)
+            report_tissue(args, tissue, slide)
             return f, None, meta
 
         f_all, _, meta = score_sharded(len(slides), score, rank, world)
@@ -332,6 +374,7 @@ def cmd_detect(args):
     geom = detect_geometry(args)
     if geom is None:
         return 2
+    tissue = tissue_filter(args)
     slides = list_slides(args, split="test")
     if not slides:
         print(f"[ERROR] No slides to detect on: '{os.path.join(data_root(args), 'test', 'img')}' holds none and no --synthetic was given.")
@@ -349,12 +392,14 @@ def cmd_detect(args):
         if slide is None:
             continue
         res = detect.detect_slide(slide, net, levels=geom.levels, cell=geom.cell, fuse=args.detect_fuse, sigma=args.detect_sigma,
-                                  radius=args.detect_radius, threshold=args.detect_threshold, max_detections=args.detect_max)
+                                  radius=args.detect_radius, threshold=args.detect_threshold, max_detections=args.detect_max,
+                                  tissue=tissue)
         n = detect.save_detection_csv(os.path.join(csv_dir, name + ".csv"), res)
         if args.detect_save_maps:
             np.save(os.path.join(map_dir, name + ".npy"), res.fused.cpu().numpy())
         print(f"[INFO] {name}: {res.probs.shape[0]} windows at levels {list(geom.levels)}, map {res.grid[0]} x {res.grid[1]} cells of "
               f"{geom.cell} px, {n} detections", flush=True)
+        report_tissue(args, tissue, slide)
     return 0
 
 
@@ -423,6 +468,11 @@ def main(argv=None) -> int:
         mil_triple(args)  # prints why; refused before any process is started or any GPU touched
         return 2
     if args.detect and detect_geometry(args) is None:  # refused before any process is started or any GPU touched
+        return 2
+    try:
+        tissue_filter(args)  # likewise
+    except ValueError as e:
+        print(f"[ERROR] --tissue_filter: {e}")
         return 2
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.world_size > 1 and not under_launcher:
