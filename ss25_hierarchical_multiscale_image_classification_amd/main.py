@@ -32,6 +32,14 @@ opening, a dilation by ``--tissue_dilate`` mask pixels, never below ``--tissue_s
 ``--tissue_min`` of its mask rectangle is tissue.  Honoured by ``--patch``, ``--extract_features`` on the fused slide route and
 ``--detect``; ``--tissue_save_masks`` writes ``./models/first_model/tissue_masks/<case>.npy`` (uint8[mh][mw]).
 
+``--stain_norm macenko`` normalises every slide's H&E colours on the device right after it is opened (``stain.py``): Macenko's
+stain vectors are fitted on the coarsest level (tissue pixels: optical density of every channel at least ``--stain_beta``, and inside
+the Otsu mask under ``--tissue_filter otsu``; the extreme angles at the ``--stain_alpha`` / 100 - ``--stain_alpha`` percentiles) and
+every level is mapped in place to the usual Macenko target, or to the ``HE`` / ``maxC`` of ``--stain_target FILE.json``;
+``--stain_save_fit`` writes ``./models/first_model/stain/<case>.json``.  Honoured by ``--patch``, ``--extract_features`` on the fused
+slide route and ``--detect``.  The Otsu mask is made from the original pixels and is not recomputed; the ``white`` rule
+(``mean > 240``) sees the normalised pixels.  Default ``none``: no byte of any output changes.
+
 ``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by ``--detect``, or by
 ``features.save_froc_csv`` with one line per window) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
@@ -138,6 +146,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tissue_dilate", type=int, default=1, help="otsu: radius of the mask's final dilation in mask pixels (0..8)")
     p.add_argument("--tissue_sat_floor", type=int, default=16, help="otsu: the saturation threshold never goes below this (0..255)")
     p.add_argument("--tissue_save_masks", action="store_true", help="otsu: also write models/first_model/tissue_masks/<case>.npy (uint8[mh][mw])")
+    p.add_argument("--stain_norm", choices=["none", "macenko"], default="none",
+                   help="macenko: fit the slide's stain vectors on the device and map every level to the target appearance in place")
+    p.add_argument("--stain_alpha", type=float, default=1.0, help="macenko: percentile of the stain angles, percent (> 0 and < 50)")
+    p.add_argument("--stain_beta", type=float, default=0.15, help="macenko: smallest optical density of a tissue pixel (> 0 and <= 1)")
+    p.add_argument("--stain_target", type=str, default=None, help="macenko: JSON with the HE and maxC to map to (written by --stain_save_fit)")
+    p.add_argument("--stain_save_fit", action="store_true", help="macenko: also write models/first_model/stain/<case>.json (HE, maxC, n, status)")
     p.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)
     return p
 
@@ -239,13 +253,49 @@ def report_tissue(args, tissue, slide):
         np.save(os.path.join(mask_dir, slide.name + ".npy"), tm.mask.cpu().numpy())
 
 
+def stain_norm(args):
+    """The ``stain.StainNorm`` of the --stain_* flags, None for the default ``none``; ValueError for a bad value or an unreadable
+    target (no GPU is touched)."""
+    from .stain import StainNorm, check_parameters, load_target
+
+    check_parameters(args.stain_alpha, args.stain_beta)  # checked whether or not the stage is on
+    target = load_target(args.stain_target) if args.stain_target else None
+    if args.stain_norm != "macenko":
+        return None
+    return StainNorm(alpha=args.stain_alpha, beta=args.stain_beta, target=target)
+
+
+def normalize_stain(args, stain, tissue, slide):
+    """--stain_norm macenko: right after the slide is opened, before anything reads its pixels (under --tissue_filter otsu the mask
+    is made first, from the original pixels, and restricts the fit).  Nothing is read back here."""
+    if stain is not None:
+        stain.normalize(slide, tissue)
+
+
+def report_stain(args, stain, tissue, slide):
+    """The per-slide line of --stain_norm macenko (and the file of --stain_save_fit); called when the slide's results are back."""
+    if stain is None:
+        return
+    fit = stain.normalize(slide, tissue)  # the fit the slide was normalised with
+    print(f"[INFO] {slide.name}: {fit.report()}", flush=True)
+    if args.stain_save_fit:
+        import json
+
+        fit_dir = os.path.join(os.getcwd(), "models", "first_model", "stain")
+        os.makedirs(fit_dir, exist_ok=True)
+        with open(os.path.join(fit_dir, slide.name + ".json"), "w") as f:
+            json.dump({**fit.to_dict(), "alpha": stain.alpha, "beta": stain.beta}, f, indent=1)
+
+
 def cmd_patch(args):
     from .dist import rank_world
     from .extract import save_patch_pngs, scan_level
 
     tissue = tissue_filter(args)
+    stain = stain_norm(args)
     rank, world = rank_world()  # N > 1: every rank extracts the slides it owns; the outputs are per-slide directories
     for _, slide in open_slides(args, rank, world):
+        normalize_stain(args, stain, tissue, slide)
         for level in levels_of(args):
             level_dir = os.path.join(data_root(args), "patches", f"level_{level}")
             save_dir = os.path.join(level_dir, slide.name)
@@ -262,6 +312,7 @@ def cmd_patch(args):
                 save_patch_pngs(slide, level, level_dir, stride=args.stride, tissue=tissue)
             print(f"[INFO] Patch extraction complete for {slide.name} at level {level}. Total patches: {n}")
         report_tissue(args, tissue, slide)
+        report_stain(args, stain, tissue, slide)
 
 
 def load_net(args, num_classes: Optional[int] = None):
@@ -294,9 +345,12 @@ def cmd_extract_features(args):
 
     rank, world = rank_world()
     tissue = tissue_filter(args)
+    stain = stain_norm(args)
     if has_png:
         if tissue is not None and rank == 0:
             print("[INFO] --tissue_filter otsu does not apply to a PNG patch tree: its patches were chosen when they were extracted")
+        if stain is not None and rank == 0:
+            print("[INFO] --stain_norm macenko does not apply to a PNG patch tree: its pixels were written when they were extracted")
         if world > 1 and rank == 0:
             print("[INFO] PNG patch tree: scored by rank 0 (the fused slide path is the one that shards)")
         if rank != 0:
@@ -315,9 +369,11 @@ def cmd_extract_features(args):
             if slide is None:  # zero rows for this unit; the exchange and the other slides go on
                 dev = torch.device("cuda", torch.cuda.current_device())
                 return torch.zeros((0, 512), dtype=torch.float32, device=dev), None, torch.zeros((0, 4), dtype=torch.int32, device=dev)
+            normalize_stain(args, stain, tissue, slide)
             f, _, _, meta = score_slide(slide, net, levels=(level,), batch_windows=512, stride=args.stride,
                                         want_logits=False, tissue=tissue)
             report_tissue(args, tissue, slide)
+            report_stain(args, stain, tissue, slide)
             return f, None, meta
 
         f_all, _, meta = score_sharded(len(slides), score, rank, world)
@@ -375,6 +431,7 @@ def cmd_detect(args):
     if geom is None:
         return 2
     tissue = tissue_filter(args)
+    stain = stain_norm(args)
     slides = list_slides(args, split="test")
     if not slides:
         print(f"[ERROR] No slides to detect on: '{os.path.join(data_root(args), 'test', 'img')}' holds none and no --synthetic was given.")
@@ -391,6 +448,7 @@ def cmd_detect(args):
         slide = try_open(name, slides[i][1])
         if slide is None:
             continue
+        normalize_stain(args, stain, tissue, slide)
         res = detect.detect_slide(slide, net, levels=geom.levels, cell=geom.cell, fuse=args.detect_fuse, sigma=args.detect_sigma,
                                   radius=args.detect_radius, threshold=args.detect_threshold, max_detections=args.detect_max,
                                   tissue=tissue)
@@ -400,6 +458,7 @@ def cmd_detect(args):
         print(f"[INFO] {name}: {res.probs.shape[0]} windows at levels {list(geom.levels)}, map {res.grid[0]} x {res.grid[1]} cells of "
               f"{geom.cell} px, {n} detections", flush=True)
         report_tissue(args, tissue, slide)
+        report_stain(args, stain, tissue, slide)
     return 0
 
 
@@ -473,6 +532,11 @@ def main(argv=None) -> int:
         tissue_filter(args)  # likewise
     except ValueError as e:
         print(f"[ERROR] --tissue_filter: {e}")
+        return 2
+    try:
+        stain_norm(args)  # likewise
+    except ValueError as e:
+        print(f"[ERROR] --stain_norm: {e}")
         return 2
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.world_size > 1 and not under_launcher:
