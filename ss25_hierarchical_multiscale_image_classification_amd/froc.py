@@ -329,7 +329,7 @@ def run_evaluation(data_root: str, cwd: Optional[str] = None, resolution: float 
                 continue
             try:
                 mask = load_case_mask(data_root, case, source, level)
-            except Exception as e:  # noqa: BLE001 -- LZW tiles, too few levels, a missing slide header: this case only
+            except Exception as e:  # noqa: BLE001 -- too few levels, a missing slide header: this case only
                 print(f"[ERROR] Could not read the mask of {case} ({source[1]}): {type(e).__name__}: {e}. Skipping.")
                 continue
             em = evaluation_mask(mask, resolution, level)

@@ -4,8 +4,8 @@ The reference opens CAMELYON16 slides with openslide (src/main.py:650-655:
 ``OpenSlide(path)``, ``level_dimensions``, ``level_downsamples``) and pulls every window
 through ``read_region(location, level, size)`` (:693-697).  openslide is not available in
 this image, so this module reads the container itself: classic TIFF and BigTIFF, tiled
-IFDs, 8-bit RGB, compression none / deflate / LZW-free JPEG (old-style excluded), one
-pyramid level per full-resolution or reduced-resolution tiled IFD, largest first
+IFDs, 8-bit RGB, compression none / deflate / LZW (TIFF 6.0, predictor none or horizontal) / JPEG (old-style
+excluded), one pyramid level per full-resolution or reduced-resolution tiled IFD, largest first
 (the "generic tiled TIFF" layout of the CAMELYON16 files).
 
 Tiles are decoded on host threads (Pillow's JPEG / zlib decoders release the GIL) in row
@@ -19,6 +19,7 @@ than one band of one level.  Semantics kept from openslide:
 """
 from __future__ import annotations
 
+import ctypes as C
 import io
 import struct
 import zlib
@@ -36,6 +37,68 @@ class TiffError(ValueError):
     pass
 
 
+LZW_ABI_VERSION = 1  # include/hipac_lzw.h HIPAC_LZW_ABI_VERSION this binding was written against
+LZW_MAX_TILE_BYTES, LZW_MAX_TILES, LZW_MAX_LEVELS = 1 << 20, 65535, 16  # HIPAC_LZW_MAX_*
+LZW_OK, LZW_REFUSED, LZW_MISSING, LZW_BAD_TILE = 0, 1, 2, 3  # status_dev values
+# name -> (restype, argtypes); must list every symbol include/hipac_lzw.h declares (tests/test_lzw_capi_symbols.py)
+LZW_SYMBOLS = {
+    "hipac_lzw_abi_version": (C.c_int, []),
+    "hipac_lzw_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hipac_lzw_decode_tiles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
+
+class LzwLevel(C.Structure):
+    """hipac_lzw_level (include/hipac_lzw.h)."""
+    _fields_ = [("pixels", C.c_void_p), ("pitch_bytes", C.c_int64), ("W", C.c_int32), ("H", C.c_int32), ("tile_w", C.c_int32),
+                ("tile_h", C.c_int32), ("samples", C.c_int32), ("predictor", C.c_int32)]
+
+
+_lzw_bound = None
+
+
+def load_lzw_library():
+    """The library of ``capi.load_library()`` with the LZW entry points bound; HipacError on a version mismatch."""
+    global _lzw_bound
+    from . import capi
+
+    lib = capi.load_library()
+    if _lzw_bound is not lib:
+        _lzw_bound = capi.bind_symbols(lib, LZW_SYMBOLS, "hipac_lzw_abi_version", LZW_ABI_VERSION, "LZW ABI")
+    return lib
+
+
+def device_lzw_tiles(file_dev, levels, off, cnt, xyl):
+    """One ``hipac_lzw_decode_tiles`` call.  ``file_dev``: uint8 tensor of the file's bytes; ``levels``: (tensor uint8[H, Wpad, 3],
+    width, height, tile_w, tile_h, samples, predictor) each; ``off`` / ``cnt``: int64[n]; ``xyl``: int32[n, 3].  Returns the
+    status of every tile as numpy uint8[n], read once after the call."""
+    import torch
+
+    from . import capi
+
+    lib = load_lzw_library()
+    device = file_dev.device
+    n = int(len(off))
+    arr = (LzwLevel * len(levels))()
+    for i, (dv, w, h, tw, th, spp, pred) in enumerate(levels):
+        arr[i] = LzwLevel(dv.data_ptr(), int(dv.stride(0)), w, h, tw, th, spp, pred)
+    tw, th, spp = max(l[3] for l in levels), max(l[4] for l in levels), max(l[5] for l in levels)
+    need = max(lib.hipac_lzw_workspace_bytes(l[3], l[4], l[5], n) for l in levels)
+    if need == 0:
+        raise TiffError(f"LZW tiles of {tw} x {th} x {spp} samples, or {n} of them in one call, are not decoded on the device")
+    with torch.cuda.device(device):
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        o = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(device)
+        c = torch.from_numpy(np.ascontiguousarray(cnt, np.int64)).to(device)
+        q = torch.from_numpy(np.ascontiguousarray(xyl, np.int32)).to(device)
+        status = torch.empty(n, dtype=torch.uint8, device=device)
+        capi._check(lib.hipac_lzw_decode_tiles(file_dev.data_ptr(), int(file_dev.numel()), C.addressof(arr), len(levels), o.data_ptr(),
+                                               c.data_ptr(), q.data_ptr(), n, ws.data_ptr(), int(ws.numel()), status.data_ptr(),
+                                               capi._stream()), "hipac_lzw_decode_tiles")
+        return status.cpu().numpy()
+
+
 @dataclass
 class TiffLevel:
     width: int
@@ -49,6 +112,7 @@ class TiffLevel:
     counts: Sequence[int]
     jpeg_tables: Optional[bytes]
     subfile_type: int
+    predictor: int = 1  # tag 317, read for LZW levels: 1 none, 2 horizontal differencing
 
     @property
     def tiles_across(self) -> int:
@@ -107,6 +171,124 @@ def _parse_ifds(buf) -> List[dict]:
     return ifds
 
 
+def lzw_decode(data, n_out: int) -> Tuple[bytes, int]:
+    """TIFF 6.0 LZW, the definition csrc/lzw.hip is compared with: (``n_out`` bytes, status).
+
+    Codes are MSB-first, 9 to 12 bits; 256 = Clear, 257 = EOI; the width grows one code early (at table sizes 511, 1023,
+    2047); the code after a Clear is a literal (further Clears are skipped, EOI ends the stream); a code equal to the next
+    free entry is the previous string plus its own first byte (KwKwK); a table filled to 4095 without a Clear stays at 12
+    bits and takes no more entries.  Decoding stops at EOI, when ``n_out`` bytes are written, or when fewer bits than one
+    code are left; what was not written is 0.  Status 1 (and all bytes 0): the first code is neither Clear nor a literal,
+    a code is larger than the next free entry, a Clear is followed by a code above 257, or the stream is of the old
+    LSB-first variant (libtiff's test: first byte 0, second byte odd)."""
+    data = bytes(data)
+    n = len(data)
+    zero = bytes(n_out)
+    if n >= 2 and data[0] == 0 and data[1] & 1:
+        return zero, 1
+    out = bytearray(n_out)
+    table = [bytes([i]) for i in range(256)] + [b"", b""]
+    pos = acc = nb = o = 0
+    width, prev, first = 9, None, True
+    while o < n_out:
+        while nb < width and pos < n:
+            acc = (acc << 8) | data[pos]
+            pos += 1
+            nb += 8
+        if nb < width:
+            break
+        nb -= width
+        code = acc >> nb
+        acc &= (1 << nb) - 1
+        if code == 257:
+            if first:
+                return zero, 1
+            break
+        first = False
+        if code == 256:
+            del table[258:]
+            width, prev = 9, None
+            continue
+        nxt = len(table)
+        if prev is None:
+            if code > 255:
+                return zero, 1
+            s = table[code]
+        else:
+            if code < nxt:
+                s = table[code]
+            elif code == nxt and nxt < 4096:
+                s = prev + prev[:1]
+            else:
+                return zero, 1
+            if nxt < 4096:
+                table.append(prev + s[:1])
+                if nxt + 2 >= 1 << width and width < 12:
+                    width += 1
+        m = min(len(s), n_out - o)
+        out[o:o + m] = s[:m]
+        o += m
+        prev = s
+    return bytes(out), 0
+
+
+def lzw_encode(data, clear_when_full: bool = True) -> bytes:
+    """The writer's LZW (tests and synthetic data): greedy longest match, Clear first and again when the table reaches
+    4094 (as libtiff does), EOI last, early change.  ``clear_when_full=False`` never clears after the first Clear: the
+    table fills to 4095 and the stream goes on at 12 bits."""
+    data = bytes(data)
+    out = bytearray()
+    acc = nb = 0
+    width, nxt = 9, 258
+
+    def emit(code):
+        nonlocal acc, nb
+        acc = (acc << width) | code
+        nb += width
+        while nb >= 8:
+            nb -= 8
+            out.append((acc >> nb) & 0xFF)
+        acc &= (1 << nb) - 1
+
+    def added():  # one more entry: the decoder gets it one code later, and both change width after the same code
+        nonlocal width, nxt
+        nxt += 1
+        if clear_when_full and nxt == 4094:
+            emit(256)
+            table.clear()
+            width, nxt = 9, 258
+        elif nxt >= 1 << width and width < 12:
+            width += 1
+
+    table = {}
+    emit(256)
+    if data:
+        w = data[0]
+        for c in data[1:]:
+            k = (w << 8) | c
+            got = table.get(k)
+            if got is not None:
+                w = got
+                continue
+            emit(w)
+            if nxt < 4096:
+                table[k] = nxt
+                added()
+            w = c
+        emit(w)
+        if nxt < 4096:
+            added()
+    emit(257)
+    if nb:
+        out.append((acc << (8 - nb)) & 0xFF)
+    return bytes(out)
+
+
+def undo_predictor(tile: np.ndarray) -> np.ndarray:
+    """Predictor 2 undone: per row and sample the running sum mod 256 over the whole tile width.  uint8[h, w, s]."""
+    return np.cumsum(tile.astype(np.uint32), axis=1).astype(np.uint8)
+
+
 def _adobe_rgb_marker() -> bytes:
     # APP14 "Adobe" with transform = 0: the three components are RGB, not YCbCr
     return b"\xff\xee\x00\x0eAdobe\x00\x64\x00\x00\x00\x00\x00"
@@ -132,8 +314,12 @@ class TiffPyramid:
             lv = TiffLevel(width=t[256][0], height=t[257][0], tile_w=t[322][0], tile_h=t[323][0],
                            compression=t.get(259, [1])[0], photometric=t.get(262, [2])[0], samples=spp,
                            offsets=t[324], counts=t[325], jpeg_tables=t.get(347), subfile_type=t.get(254, [0])[0])
-            if lv.compression not in (1, 7, 8, 32946):
-                raise TiffError(f"unsupported tile compression {lv.compression} (none, JPEG and deflate are read)")
+            if lv.compression not in (1, 5, 7, 8, 32946):
+                raise TiffError(f"unsupported tile compression {lv.compression} (none, LZW, JPEG and deflate are read)")
+            if lv.compression == 5:
+                lv.predictor = t.get(317, [1])[0]
+                if lv.predictor not in (1, 2):
+                    raise TiffError(f"unsupported LZW predictor {lv.predictor} (1 = none and 2 = horizontal are read)")
             levels.append(lv)
         if not levels:
             raise TiffError(f"no tiled 8-bit image directory with {' or '.join(map(str, samples))} samples per pixel found")
@@ -155,6 +341,11 @@ class TiffPyramid:
             a = np.frombuffer(raw, np.uint8)
         elif lv.compression in (8, 32946):
             a = np.frombuffer(zlib.decompress(raw), np.uint8)
+        elif lv.compression == 5:
+            data, status = lzw_decode(raw, lv.tile_h * lv.tile_w * lv.samples)
+            self.lzw_refused = getattr(self, "lzw_refused", 0) + status  # a refused tile is all 0
+            a = np.frombuffer(data, np.uint8).reshape(lv.tile_h, lv.tile_w, lv.samples)
+            return (undo_predictor(a) if lv.predictor == 2 else a)[:, :, :3]
         else:
             from PIL import Image
 
@@ -268,12 +459,47 @@ class TiffPyramid:
                 self.device_decoded = getattr(self, "device_decoded", 0) + int((status == 0).sum())
         return left
 
+    def _device_lzw_levels(self, lvs, devs, step: int = 16384):
+        """LZW tiles of the given levels decoded on the device (csrc/lzw.hip: one wavefront per tile, then the predictor and
+        the placement), written into ``devs`` (uint8[H, Wpad, 3] each).  The file's bytes go to HBM as they are, without slack:
+        the kernels check every read.  Tiles of all levels share the calls.  Returns the number of tiles the decoder refused
+        (status 1: malformed streams; their pixels are 0 -- the host decoder is the same definition and refuses them too)."""
+        import warnings
+
+        import torch
+
+        device = devs[0].device
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # "the given NumPy array is not writable": it is only read
+            file_dev = torch.from_numpy(self._mm).to(device)
+        table = [(dv, lv.width, lv.height, lv.tile_w, lv.tile_h, lv.samples, lv.predictor) for lv, dv in zip(lvs, devs)]
+        off, cnt, xyl = [], [], []
+        for i, lv in enumerate(lvs):
+            n = lv.tiles_across * lv.tiles_down
+            k = np.arange(n)
+            off.append(np.asarray(lv.offsets[:n], np.int64)), cnt.append(np.asarray(lv.counts[:n], np.int64))
+            xyl.append(np.stack([(k % lv.tiles_across) * lv.tile_w, (k // lv.tiles_across) * lv.tile_h, np.full(n, i)], 1).astype(np.int32))
+        off, cnt, xyl = np.concatenate(off), np.concatenate(cnt), np.concatenate(xyl)
+        per_tile = max(lv.tile_w * lv.tile_h * lv.samples for lv in lvs)
+        free, _ = torch.cuda.mem_get_info(device)
+        step = int(max(1, min(step, LZW_MAX_TILES, (free // 2) // max(per_tile, 1))))
+        refused = 0
+        for i0 in range(0, off.shape[0], step):
+            status = device_lzw_tiles(file_dev, table, off[i0:i0 + step], cnt[i0:i0 + step], xyl[i0:i0 + step])
+            if (status == LZW_BAD_TILE).any():
+                raise TiffError(f"{self.path}: {int((status == LZW_BAD_TILE).sum())} LZW tiles lie outside the file")
+            refused += int((status == LZW_REFUSED).sum())
+            self.device_decoded = getattr(self, "device_decoded", 0) + int((status == LZW_OK).sum())
+        return refused
+
     def to_device_levels(self, device="cuda", levels: Optional[Sequence[int]] = None, workers: int = 16,
-                         device_jpeg: Optional[bool] = None):
+                         device_jpeg: Optional[bool] = None, device_lzw: Optional[bool] = None):
         """Into uint8[H, Wpad, 3] HBM tensors (row pitch a multiple of 16 pixels, as ``DeviceSlide`` lays levels out).
         JPEG levels on a ROCm device: the compressed file goes to HBM once and the tiles are decoded there
         (``_device_jpeg_levels``; ``device_jpeg=False`` or ``HIPAC_DEVICE_JPEG=0`` keeps the host decoder); tiles the device
         decoder does not take, and the other compressions, are decoded on host threads and copied band by band.
+        LZW levels of any sample count on a ROCm device are decoded there as well (``_device_lzw_levels``; ``device_lzw=False``
+        or ``HIPAC_DEVICE_LZW=0`` keeps the host decoder); malformed LZW tiles stay 0 and are reported once, as a count.
         Returns a list of (tensor, width)."""
         import os
 
@@ -289,6 +515,11 @@ class TiffPyramid:
             bufs[li] = torch.zeros((lv.height, (lv.width + 15) // 16 * 16, 3), dtype=torch.uint8, device=device)
         on_dev = [li for li in use if use_dev and self.levels[li].compression == 7 and self.levels[li].samples == 3]
         left = dict(zip(on_dev, self._device_jpeg_levels([self.levels[li] for li in on_dev], [bufs[li] for li in on_dev]))) if on_dev else {}
+        use_lzw = (device_lzw if device_lzw is not None else os.environ.get("HIPAC_DEVICE_LZW", "1") != "0") and \
+            torch.device(device).type == "cuda"
+        lzw_dev = [li for li in use if use_lzw and self.levels[li].compression == 5]
+        host_refused = getattr(self, "lzw_refused", 0)
+        refused = self._device_lzw_levels([self.levels[li] for li in lzw_dev], [bufs[li] for li in lzw_dev]) if lzw_dev else 0
         with ThreadPoolExecutor(max_workers=workers) as pool:
             for li in use:
                 lv = self.levels[li]
@@ -304,6 +535,9 @@ class TiffPyramid:
                         dev[y0:y0 + rows, x0:x0 + cols] = torch.from_numpy(np.ascontiguousarray(t[:rows, :cols])).to(device)
                     out.append((dev, lv.width))
                     continue
+                if li in lzw_dev:
+                    out.append((dev, lv.width))
+                    continue
                 for tr in range(lv.tiles_down):
                     band = torch.from_numpy(self.read_band(li, tr, pool))
                     if dev.is_cuda:
@@ -311,18 +545,35 @@ class TiffPyramid:
                     y0 = tr * lv.tile_h
                     dev[y0:y0 + band.shape[0], :lv.width].copy_(band, non_blocking=False)
                 out.append((dev, lv.width))
+        refused += getattr(self, "lzw_refused", 0) - host_refused
+        if refused:
+            print(f"{self.path}: {refused} malformed LZW tiles were not decoded and stay 0.")
         return out
+
+
+def _rocm_device_present() -> bool:
+    import os
+
+    if os.environ.get("HIPAC_DEVICE_LZW", "1") == "0":
+        return False
+    import torch
+
+    return torch.cuda.is_available()
 
 
 def read_mask_level(path: str, level: int) -> np.ndarray:
     """uint8[H, W] of level ``level`` of an evaluation mask, channel 0 of openslide's ``read_region((0, 0), level, dims)``
     (evaluation_FROC.py:29-30): tiled 8-bit grayscale (1 sample, the value itself), RGB or RGBA (the red sample)
-    directories; compression none, deflate or JPEG.  TiffError for LZW and for a file with fewer than ``level + 1``
-    levels."""
+    directories; compression none, deflate, LZW or JPEG.  An LZW level is decoded on the device when a ROCm device is
+    present (``HIPAC_DEVICE_LZW=0`` keeps the host decoder) and channel 0 is copied back.  TiffError for a file with fewer
+    than ``level + 1`` levels."""
     p = TiffPyramid(path, samples=(1, 3, 4))
     if level >= p.level_count:
         raise TiffError(f"{path} has {p.level_count} levels, level {level} was asked for")
     lv = p.levels[level]
+    if lv.compression == 5 and _rocm_device_present():
+        (dev, width), = p.to_device_levels("cuda", [level])
+        return dev[:, :width, 0].contiguous().cpu().numpy()
     out = np.zeros((lv.height, lv.width), np.uint8)
     for tr in range(lv.tiles_down):
         band = p.read_band(level, tr)
@@ -355,14 +606,19 @@ def _split_jpeg_tables(data: bytes) -> Tuple[bytes, bytes]:
 
 def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, compression: str = "jpeg",
                      quality: int = 90, bigtiff: bool = False, missing: Sequence[Tuple[int, int, int]] = (),
-                     jpeg_tables: bool = False, subsampling: int = -1, jpeg_options: Optional[dict] = None):
+                     jpeg_tables: bool = False, subsampling: int = -1, jpeg_options: Optional[dict] = None,
+                     predictor: int = 1, clear_when_full: bool = True):
     """Minimal writer of a tiled pyramid (tests and synthetic data only): ``levels`` are uint8[H,W,3]
     arrays, or uint8[H,W] for single-sample (grayscale, MinIsBlack) directories, largest first.  compression: "none" | "deflate" | "jpeg" (YCbCr; every tile a complete JPEG, or with
     ``jpeg_tables=True`` abbreviated streams plus one JPEGTables tag per directory, as real slide files have
-    them).  ``missing``: (level, ty, tx) tiles written with byte count 0."""
+    them).  ``missing``: (level, ty, tx) tiles written with byte count 0.  "lzw": ``lzw_encode`` streams, ``predictor`` 1 (tag 317
+    absent) or 2 (horizontal differencing over the padded tile); uint8[H,W,4] levels (RGB + unassociated alpha) are
+    written with 4 samples for every compression but JPEG."""
     from PIL import Image
 
-    comp = {"none": 1, "deflate": 8, "jpeg": 7}[compression]
+    comp = {"none": 1, "deflate": 8, "jpeg": 7, "lzw": 5}[compression]
+    if predictor not in (1, 2) or (predictor == 2 and comp != 5):
+        raise TiffError("predictor 2 is written for LZW only")
     bo = "<"
     blobs, ifd_specs = [], []
     pos = 16 if bigtiff else 8
@@ -377,13 +633,19 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                 if (li, ty, tx) in missing:
                     offs.append(0), cnts.append(0)
                     continue
-                t = np.zeros((tile, tile) if img.ndim == 2 else (tile, tile, 3), np.uint8)
+                t = np.zeros((tile, tile) if img.ndim == 2 else (tile, tile, img.shape[2]), np.uint8)
                 part = img[ty * tile:(ty + 1) * tile, tx * tile:(tx + 1) * tile]
                 t[:part.shape[0], :part.shape[1]] = part
                 if comp == 1:
                     data = t.tobytes()
                 elif comp == 8:
                     data = zlib.compress(t.tobytes(), 6)
+                elif comp == 5:
+                    if predictor == 2:
+                        d = t.reshape(tile, tile, -1).copy()
+                        d[:, 1:] -= t.reshape(tile, tile, -1)[:, :-1]
+                        t = d
+                    data = lzw_encode(t.tobytes(), clear_when_full)
                 else:
                     bio = io.BytesIO()
                     Image.fromarray(t, "L" if img.ndim == 2 else "RGB").save(bio, "JPEG", quality=quality, subsampling=subsampling, **(jpeg_options or {}))
@@ -396,7 +658,7 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                 offs.append(pos), cnts.append(len(data))
                 blobs.append(data)
                 pos += len(data)
-        ifd_specs.append((w, h, ta * td, offs, cnts, 1 if img.ndim == 2 else 3))
+        ifd_specs.append((w, h, ta * td, offs, cnts, 1 if img.ndim == 2 else img.shape[2]))
         tables_of_level.append(level_tables)
     out = bytearray()
     # data area first, then IFDs (offsets known up front)
@@ -409,6 +671,10 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
         entries = [(254, 4, [1 if li else 0]), (256, 4, [w]), (257, 4, [h]), (258, 3, [8] * spp), (259, 3, [comp]),
                    (262, 3, [photometric]), (277, 3, [spp]), (284, 3, [1]), (322, 4, [tile]), (323, 4, [tile]),
                    (324, 16 if bigtiff else 4, offs), (325, 16 if bigtiff else 4, cnts)]
+        if predictor == 2:
+            entries.insert(8, (317, 3, [2]))  # Predictor, between 284 and 322: tags stay sorted
+        if spp == 4:
+            entries.append((338, 3, [2]))  # ExtraSamples: unassociated alpha
         if tables_of_level[li] is not None:
             entries.append((347, 7, list(tables_of_level[li])))  # JPEGTables (UNDEFINED bytes); tags stay sorted
         n = len(entries)

@@ -1,6 +1,8 @@
 """Developer tool (GPU box): how fast a tiled pyramidal TIFF gets into HBM (tiff_pyramid.TiffPyramid.to_device_levels:
 tiles decoded on host threads, copied band by band) next to the scan of the same slide.
-usage: python tools/tiffbench.py [side] [compression: jpeg|deflate|none] [workers]"""
+usage: python tools/tiffbench.py [side] [compression: jpeg|deflate|none|lzw] [workers] [--compression lzw]
+With LZW the tool compares the device decoder (csrc/lzw.hip) with the host decoder on ``workers`` threads on the same file:
+median of 5 loads each, modes alternated (the writer's LZW encoder is plain Python: keep ``side`` small, default 2048)."""
 import os
 import sys
 import tempfile
@@ -11,9 +13,15 @@ import torch  # noqa: E402
 
 from ss25_hierarchical_multiscale_image_classification_amd import capi, extract, synth, tiff_pyramid  # noqa: E402
 
-side = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
-comp = sys.argv[2] if len(sys.argv) > 2 else "jpeg"
-workers = int(sys.argv[3]) if len(sys.argv) > 3 else 16
+argv = list(sys.argv[1:])
+flag = None
+if "--compression" in argv:
+    k = argv.index("--compression")
+    flag = argv[k + 1]
+    del argv[k:k + 2]
+comp = flag or (argv[1] if len(argv) > 1 else "jpeg")
+side = int(argv[0]) if argv else (2048 if comp == "lzw" else 20000)
+workers = int(argv[2]) if len(argv) > 2 else 16
 l0 = synth.synth_level0(side, side, seed=2, device="cuda")
 levels = [t.cpu().numpy() for t in synth.build_pyramid(l0, 4)]
 path = os.path.join(tempfile.mkdtemp(prefix="hipac_tiff_"), "slide.tif")
@@ -21,6 +29,25 @@ t = time.perf_counter()
 tiff_pyramid.write_tiled_tiff(path, levels, tile=512, compression=comp)
 print(f"wrote {path}: {os.path.getsize(path) / 1e6:.0f} MB in {time.perf_counter() - t:.1f} s")
 del l0, levels
+if comp == "lzw":
+    import statistics
+
+    times = {True: [], False: []}
+    tp = tiff_pyramid.TiffPyramid(path)
+    px = sum(w * h for w, h in tp.level_dimensions)
+    tp.to_device_levels("cuda", device_lzw=True)  # the first call loads the code object
+    for rep in range(5):
+        for on_device in (True, False):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = tiff_pyramid.TiffPyramid(path).to_device_levels("cuda", workers=workers, device_lzw=on_device)
+            torch.cuda.synchronize()
+            times[on_device].append(time.perf_counter() - t)
+            del out
+    for on_device, name in ((True, "device"), (False, f"host, {workers} threads")):
+        m = statistics.median(times[on_device])
+        print(f"to_device_levels (lzw, {name}): median of 5 {m:.3f} s = {px / 1e6 / m:.1f} Mpx/s  {[round(x, 3) for x in times[on_device]]}")
+    sys.exit(0)
 for rep in range(2):
     t = time.perf_counter()
     slide = extract.DeviceSlide.from_tiff(path, workers=workers)
