@@ -4,7 +4,7 @@ The reference opens CAMELYON16 slides with openslide (src/main.py:650-655:
 ``OpenSlide(path)``, ``level_dimensions``, ``level_downsamples``) and pulls every window
 through ``read_region(location, level, size)`` (:693-697).  openslide is not available in
 this image, so this module reads the container itself: classic TIFF and BigTIFF, tiled
-IFDs, 8-bit RGB, compression none / deflate / LZW (TIFF 6.0, predictor none or horizontal) / JPEG (old-style
+IFDs, 8-bit RGB, compression none / deflate and LZW (TIFF 6.0; predictor none or horizontal) / JPEG (old-style
 excluded), one pyramid level per full-resolution or reduced-resolution tiled IFD, largest first
 (the "generic tiled TIFF" layout of the CAMELYON16 files).
 
@@ -55,7 +55,25 @@ class LzwLevel(C.Structure):
                 ("tile_h", C.c_int32), ("samples", C.c_int32), ("predictor", C.c_int32)]
 
 
+DEFLATE_ABI_VERSION = 1  # include/hipac_deflate.h HIPAC_DEFLATE_ABI_VERSION this binding was written against
+DEFLATE_MAX_TILE_BYTES, DEFLATE_MAX_TILES, DEFLATE_MAX_LEVELS = 1 << 20, 65535, 16  # HIPAC_DEFLATE_MAX_*
+DEFLATE_OK, DEFLATE_REFUSED, DEFLATE_MISSING, DEFLATE_BAD_TILE = 0, 1, 2, 3  # status_dev values
+# name -> (restype, argtypes); must list every symbol include/hipac_deflate.h declares (tests/test_deflate_capi_symbols.py)
+DEFLATE_SYMBOLS = {
+    "hipac_deflate_abi_version": (C.c_int, []),
+    "hipac_deflate_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hipac_deflate_decode_tiles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
+
+class DeflateLevel(C.Structure):
+    """hipac_deflate_level (include/hipac_deflate.h): the fields of hipac_lzw_level."""
+    _fields_ = LzwLevel._fields_
+
+
 _lzw_bound = None
+_deflate_bound = None
 
 
 def load_lzw_library():
@@ -99,6 +117,53 @@ def device_lzw_tiles(file_dev, levels, off, cnt, xyl):
         return status.cpu().numpy()
 
 
+def deflate_level_on_device(lv) -> bool:
+    """Whether the device decoder takes the tiles of ``lv`` (a TiffLevel with compression 8 or 32946): the limits of
+    include/hipac_deflate.h.  Other levels stay with zlib on host threads, as all deflate levels did before."""
+    return lv.samples in (1, 3, 4) and lv.predictor in (1, 2) and 1 <= lv.tile_w * lv.tile_h * lv.samples <= DEFLATE_MAX_TILE_BYTES
+
+
+def load_deflate_library():
+    """The library of ``capi.load_library()`` with the deflate entry points bound; HipacError on a version mismatch."""
+    global _deflate_bound
+    from . import capi
+
+    lib = capi.load_library()
+    if _deflate_bound is not lib:
+        _deflate_bound = capi.bind_symbols(lib, DEFLATE_SYMBOLS, "hipac_deflate_abi_version", DEFLATE_ABI_VERSION, "deflate ABI")
+    return lib
+
+
+def device_deflate_tiles(file_dev, levels, off, cnt, xyl):
+    """One ``hipac_deflate_decode_tiles`` call; the arguments and the result are those of ``device_lzw_tiles``."""
+    import torch
+
+    from . import capi
+
+    lib = load_deflate_library()
+    device = file_dev.device
+    n = int(len(off))
+    arr = (DeflateLevel * len(levels))()
+    for i, (dv, w, h, tw, th, spp, pred) in enumerate(levels):
+        arr[i] = DeflateLevel(dv.data_ptr(), int(dv.stride(0)), w, h, tw, th, spp, pred)
+    need = 0
+    for _, _, _, tw, th, spp, _ in levels:  # each level by itself: one the decoder refuses is not hidden by the others
+        one = lib.hipac_deflate_workspace_bytes(tw, th, spp, n)
+        if one == 0:
+            raise TiffError(f"deflate tiles of {tw} x {th} x {spp} samples, or {n} of them in one call, are not decoded on the device")
+        need = max(need, one)
+    with torch.cuda.device(device):
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        o = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(device)
+        c = torch.from_numpy(np.ascontiguousarray(cnt, np.int64)).to(device)
+        q = torch.from_numpy(np.ascontiguousarray(xyl, np.int32)).to(device)
+        status = torch.empty(n, dtype=torch.uint8, device=device)
+        capi._check(lib.hipac_deflate_decode_tiles(file_dev.data_ptr(), int(file_dev.numel()), C.addressof(arr), len(levels), o.data_ptr(),
+                                                   c.data_ptr(), q.data_ptr(), n, ws.data_ptr(), int(ws.numel()), status.data_ptr(),
+                                                   capi._stream()), "hipac_deflate_decode_tiles")
+        return status.cpu().numpy()
+
+
 @dataclass
 class TiffLevel:
     width: int
@@ -112,7 +177,7 @@ class TiffLevel:
     counts: Sequence[int]
     jpeg_tables: Optional[bytes]
     subfile_type: int
-    predictor: int = 1  # tag 317, read for LZW levels: 1 none, 2 horizontal differencing
+    predictor: int = 1  # tag 317, read for LZW and deflate levels: 1 none, 2 horizontal differencing
 
     @property
     def tiles_across(self) -> int:
@@ -232,6 +297,163 @@ def lzw_decode(data, n_out: int) -> Tuple[bytes, int]:
     return bytes(out), 0
 
 
+_LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+_LEN_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+_DIST_BASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
+              12289, 16385, 24577)
+_DIST_EXTRA = (0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13)
+_CODE_LENGTH_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+_FIXED_LENGTHS = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
+
+
+class _Refused(Exception):
+    pass
+
+
+def _huffman_code(lengths, kind: str) -> dict:
+    """Canonical Huffman code of RFC 1951 3.2.2 as {(length, code read MSB first): symbol}, with zlib's admission rules:
+    an over-subscribed set is refused; an incomplete one is refused too, except a literal/length or distance set that
+    consists of a single one-bit code, and a distance set without any code (a block of literals only).  A bit pattern no
+    code owns is not in the table: reading it is a refusal.  ``kind``: "codes" | "lens" | "dists"."""
+    count = [0] * 16
+    for l in lengths:
+        count[l] += 1
+    count[0] = 0
+    left = 1
+    for l in range(1, 16):
+        left = 2 * left - count[l]
+        if left < 0:
+            raise _Refused
+    longest = max((l for l in range(1, 16) if count[l]), default=0)
+    if left > 0 and (kind == "codes" or longest > 1 or (longest == 0 and kind != "dists")):
+        raise _Refused  # (a code-length code without codes cannot describe an end-of-block code: zlib fails later, always)
+    nxt, code = [0] * 16, 0
+    for l in range(1, 16):
+        code = (code + count[l - 1]) << 1
+        nxt[l] = code
+    table = {}
+    for sym, l in enumerate(lengths):
+        if l:
+            table[(l, nxt[l])] = sym
+            nxt[l] += 1
+    return table
+
+
+def inflate(data, n_out: int) -> Tuple[bytes, int]:
+    """A zlib stream (RFC 1950 around RFC 1951), the definition csrc/deflate.hip is compared with: (``n_out`` bytes, status).
+
+    Status 0: the header is valid (CM = 8, CINFO <= 7, (CMF * 256 + FLG) % 31 == 0, FDICT = 0), every block is well-formed,
+    exactly ``n_out`` bytes come out and the big-endian Adler-32 behind the last block matches; bytes behind the checksum
+    are ignored, as ``zlib.decompress`` ignores them.  Everything else is status 1 with all bytes 0: block type 3; a stored
+    block whose LEN and ~NLEN disagree; more than 286 literal/length or 30 distance code lengths; code-length sets zlib
+    rejects (``_huffman_code``); a repeat code without a previous length or past HLIT + HDIST; no end-of-block code; a bit
+    pattern no code owns; length symbols 286 and 287, distance symbols 30 and 31; a distance beyond the bytes written so
+    far; input that ends mid-stream; output beyond ``n_out`` or short of it; a checksum mismatch.  Production decoding
+    stays with ``zlib.decompress``: this restatement is what the tests compare the kernel, and zlib, with."""
+    data = bytes(data)
+    n = len(data)
+    out = bytearray()
+    pos = 0  # in bits
+
+    def bits(k: int) -> int:
+        nonlocal pos
+        if pos + k > 8 * n:
+            raise _Refused  # input ends mid-stream
+        v = (int.from_bytes(data[pos >> 3:(pos >> 3) + 4], "little") >> (pos & 7)) & ((1 << k) - 1)  # k <= 16
+        pos += k
+        return v
+
+    def symbol(table: dict) -> int:
+        nonlocal pos
+        ahead = int.from_bytes(data[pos >> 3:(pos >> 3) + 4], "little") >> (pos & 7)  # bits behind the end read as 0
+        code = 0
+        for l in range(1, 16):
+            code = (code << 1) | (ahead & 1)
+            ahead >>= 1
+            sym = table.get((l, code))
+            if sym is not None:
+                if pos + l > 8 * n:
+                    raise _Refused  # input ends mid-stream
+                pos += l
+                return sym
+        raise _Refused  # a bit pattern no code owns, or the input ends
+
+    try:
+        if n < 2 or (data[0] * 256 + data[1]) % 31 or data[0] & 15 != 8 or data[0] >> 4 > 7 or data[1] & 32:
+            raise _Refused
+        pos = 16
+        final = 0
+        while not final:
+            final, kind = bits(1), bits(2)
+            if kind == 0:
+                pos = (pos + 7) & ~7
+                length, inverse = bits(16), bits(16)
+                if length != inverse ^ 0xFFFF or pos + 8 * length > 8 * n or len(out) + length > n_out:
+                    raise _Refused
+                out += data[pos >> 3:(pos >> 3) + length]
+                pos += 8 * length
+                continue
+            if kind == 3:
+                raise _Refused
+            if kind == 1:
+                lens, dists = _huffman_code(_FIXED_LENGTHS, "lens"), _huffman_code([5] * 32, "dists")
+            else:
+                hlit, hdist, hclen = bits(5) + 257, bits(5) + 1, bits(4) + 4
+                if hlit > 286 or hdist > 30:
+                    raise _Refused
+                cl = [0] * 19
+                for i in range(hclen):
+                    cl[_CODE_LENGTH_ORDER[i]] = bits(3)
+                codes = _huffman_code(cl, "codes")
+                lengths = []
+                while len(lengths) < hlit + hdist:
+                    sym = symbol(codes)
+                    if sym < 16:
+                        lengths.append(sym)
+                        continue
+                    if sym == 16:
+                        if not lengths:
+                            raise _Refused
+                        value, repeat = lengths[-1], 3 + bits(2)
+                    else:
+                        value, repeat = 0, 3 + bits(3) if sym == 17 else 11 + bits(7)
+                    if len(lengths) + repeat > hlit + hdist:
+                        raise _Refused
+                    lengths += [value] * repeat
+                if lengths[256] == 0:
+                    raise _Refused
+                lens, dists = _huffman_code(lengths[:hlit], "lens"), _huffman_code(lengths[hlit:], "dists")
+            while True:
+                sym = symbol(lens)
+                if sym < 256:
+                    if len(out) >= n_out:
+                        raise _Refused
+                    out.append(sym)
+                    continue
+                if sym == 256:
+                    break
+                if sym > 285:
+                    raise _Refused
+                length = _LEN_BASE[sym - 257] + bits(_LEN_EXTRA[sym - 257])
+                sym = symbol(dists)
+                if sym > 29:
+                    raise _Refused
+                dist = _DIST_BASE[sym] + bits(_DIST_EXTRA[sym])
+                if dist > len(out) or len(out) + length > n_out:
+                    raise _Refused
+                for _ in range(length):
+                    out.append(out[-dist])  # byte-serial: an overlapping copy repeats what it has just written
+        pos = (pos + 7) & ~7
+        check = bits(8) << 24 | bits(8) << 16 | bits(8) << 8 | bits(8)
+        s1 = (1 + sum(out)) % 65521
+        s2 = (len(out) + sum((len(out) - i) * b for i, b in enumerate(out))) % 65521
+        if len(out) != n_out or check != (s2 << 16 | s1):
+            raise _Refused
+    except _Refused:
+        return bytes(n_out), DEFLATE_REFUSED
+    return bytes(out), DEFLATE_OK
+
+
 def lzw_encode(data, clear_when_full: bool = True) -> bytes:
     """The writer's LZW (tests and synthetic data): greedy longest match, Clear first and again when the table reaches
     4094 (as libtiff does), EOI last, early change.  ``clear_when_full=False`` never clears after the first Clear: the
@@ -316,10 +538,11 @@ class TiffPyramid:
                            offsets=t[324], counts=t[325], jpeg_tables=t.get(347), subfile_type=t.get(254, [0])[0])
             if lv.compression not in (1, 5, 7, 8, 32946):
                 raise TiffError(f"unsupported tile compression {lv.compression} (none, LZW, JPEG and deflate are read)")
-            if lv.compression == 5:
+            if lv.compression in (5, 8, 32946):
                 lv.predictor = t.get(317, [1])[0]
                 if lv.predictor not in (1, 2):
-                    raise TiffError(f"unsupported LZW predictor {lv.predictor} (1 = none and 2 = horizontal are read)")
+                    raise TiffError(f"unsupported {'LZW' if lv.compression == 5 else 'deflate'} predictor {lv.predictor} "
+                                    "(1 = none and 2 = horizontal are read)")
             levels.append(lv)
         if not levels:
             raise TiffError(f"no tiled 8-bit image directory with {' or '.join(map(str, samples))} samples per pixel found")
@@ -362,7 +585,7 @@ class TiffPyramid:
                 raise TiffError("JPEG tile size does not match the directory")
             return a
         a = a[: lv.tile_h * lv.tile_w * lv.samples].reshape(lv.tile_h, lv.tile_w, lv.samples)
-        return a[:, :, :3]
+        return (undo_predictor(a) if lv.predictor == 2 else a)[:, :, :3]  # a deflate level may carry predictor 2
 
     def read_band(self, level: int, tile_row: int, pool: Optional[ThreadPoolExecutor] = None) -> np.ndarray:
         """uint8[rows, width, 3] of one row of tiles (clipped to the level), missing tiles = 0."""
@@ -492,14 +715,55 @@ class TiffPyramid:
             self.device_decoded = getattr(self, "device_decoded", 0) + int((status == LZW_OK).sum())
         return refused
 
+    def _device_deflate_levels(self, lvs, devs, step: int = 16384):
+        """Deflate tiles of the given levels decoded on the device (csrc/deflate.hip: one wavefront per tile, then the
+        predictor and the placement), written into ``devs`` as ``_device_lzw_levels`` does.  Returns, per level, the indices of
+        the tiles the device refused (status 1; their pixels are 0 so far): the caller hands those to the host decoder, as it
+        does with the tiles ``_device_jpeg_levels`` leaves, so a stream zlib takes is never lost and one it rejects raises
+        what it raised before."""
+        import warnings
+
+        import torch
+
+        device = devs[0].device
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # "the given NumPy array is not writable": it is only read
+            file_dev = torch.from_numpy(self._mm).to(device)
+        table = [(dv, lv.width, lv.height, lv.tile_w, lv.tile_h, lv.samples, lv.predictor) for lv, dv in zip(lvs, devs)]
+        off, cnt, xyl, lvl_of, idx_of = [], [], [], [], []
+        for i, lv in enumerate(lvs):
+            n = lv.tiles_across * lv.tiles_down
+            k = np.arange(n)
+            off.append(np.asarray(lv.offsets[:n], np.int64)), cnt.append(np.asarray(lv.counts[:n], np.int64))
+            xyl.append(np.stack([(k % lv.tiles_across) * lv.tile_w, (k // lv.tiles_across) * lv.tile_h, np.full(n, i)], 1).astype(np.int32))
+            lvl_of.append(np.full(n, i)), idx_of.append(k)
+        off, cnt, xyl = np.concatenate(off), np.concatenate(cnt), np.concatenate(xyl)
+        lvl_of, idx_of = np.concatenate(lvl_of), np.concatenate(idx_of)
+        per_tile = max(lv.tile_w * lv.tile_h * lv.samples for lv in lvs)
+        free, _ = torch.cuda.mem_get_info(device)
+        step = int(max(1, min(step, DEFLATE_MAX_TILES, (free // 2) // max(per_tile, 1))))
+        left = [[] for _ in lvs]
+        for i0 in range(0, off.shape[0], step):
+            status = device_deflate_tiles(file_dev, table, off[i0:i0 + step], cnt[i0:i0 + step], xyl[i0:i0 + step])
+            if (status == DEFLATE_BAD_TILE).any():
+                raise TiffError(f"{self.path}: {int((status == DEFLATE_BAD_TILE).sum())} deflate tiles lie outside the file")
+            for k in np.nonzero(status == DEFLATE_REFUSED)[0]:
+                left[int(lvl_of[i0 + k])].append(int(idx_of[i0 + k]))
+            self.device_decoded = getattr(self, "device_decoded", 0) + int((status == DEFLATE_OK).sum())
+        return left
+
     def to_device_levels(self, device="cuda", levels: Optional[Sequence[int]] = None, workers: int = 16,
-                         device_jpeg: Optional[bool] = None, device_lzw: Optional[bool] = None):
+                         device_jpeg: Optional[bool] = None, device_lzw: Optional[bool] = None,
+                         device_deflate: Optional[bool] = None):
         """Into uint8[H, Wpad, 3] HBM tensors (row pitch a multiple of 16 pixels, as ``DeviceSlide`` lays levels out).
         JPEG levels on a ROCm device: the compressed file goes to HBM once and the tiles are decoded there
         (``_device_jpeg_levels``; ``device_jpeg=False`` or ``HIPAC_DEVICE_JPEG=0`` keeps the host decoder); tiles the device
         decoder does not take, and the other compressions, are decoded on host threads and copied band by band.
         LZW levels of any sample count on a ROCm device are decoded there as well (``_device_lzw_levels``; ``device_lzw=False``
         or ``HIPAC_DEVICE_LZW=0`` keeps the host decoder); malformed LZW tiles stay 0 and are reported once, as a count.
+        Deflate levels (compression 8 and 32946) likewise (``_device_deflate_levels``; ``device_deflate=False`` or
+        ``HIPAC_DEVICE_DEFLATE=0`` keeps ``zlib.decompress`` on host threads); tiles the device refuses, and levels whose tiles
+        are larger than the device decoder takes (``deflate_level_on_device``), go to the host decoder.
         Returns a list of (tensor, width)."""
         import os
 
@@ -518,6 +782,12 @@ class TiffPyramid:
         use_lzw = (device_lzw if device_lzw is not None else os.environ.get("HIPAC_DEVICE_LZW", "1") != "0") and \
             torch.device(device).type == "cuda"
         lzw_dev = [li for li in use if use_lzw and self.levels[li].compression == 5]
+        use_deflate = (device_deflate if device_deflate is not None else os.environ.get("HIPAC_DEVICE_DEFLATE", "1") != "0") and \
+            torch.device(device).type == "cuda"
+        deflate_dev = [li for li in use if use_deflate and self.levels[li].compression in (8, 32946) and deflate_level_on_device(self.levels[li])]
+        for i0 in range(0, len(deflate_dev), DEFLATE_MAX_LEVELS):  # a call takes DEFLATE_MAX_LEVELS levels
+            part = deflate_dev[i0:i0 + DEFLATE_MAX_LEVELS]
+            left.update(zip(part, self._device_deflate_levels([self.levels[li] for li in part], [bufs[li] for li in part])))
         host_refused = getattr(self, "lzw_refused", 0)
         refused = self._device_lzw_levels([self.levels[li] for li in lzw_dev], [bufs[li] for li in lzw_dev]) if lzw_dev else 0
         with ThreadPoolExecutor(max_workers=workers) as pool:
@@ -551,10 +821,10 @@ class TiffPyramid:
         return out
 
 
-def _rocm_device_present() -> bool:
+def _rocm_device_present(switch: str = "HIPAC_DEVICE_LZW") -> bool:
     import os
 
-    if os.environ.get("HIPAC_DEVICE_LZW", "1") == "0":
+    if os.environ.get(switch, "1") == "0":
         return False
     import torch
 
@@ -564,14 +834,14 @@ def _rocm_device_present() -> bool:
 def read_mask_level(path: str, level: int) -> np.ndarray:
     """uint8[H, W] of level ``level`` of an evaluation mask, channel 0 of openslide's ``read_region((0, 0), level, dims)``
     (evaluation_FROC.py:29-30): tiled 8-bit grayscale (1 sample, the value itself), RGB or RGBA (the red sample)
-    directories; compression none, deflate, LZW or JPEG.  An LZW level is decoded on the device when a ROCm device is
-    present (``HIPAC_DEVICE_LZW=0`` keeps the host decoder) and channel 0 is copied back.  TiffError for a file with fewer
+    directories; compression none, deflate, LZW or JPEG.  An LZW or deflate level is decoded on the device when a ROCm device
+    is present (``HIPAC_DEVICE_LZW=0`` / ``HIPAC_DEVICE_DEFLATE=0`` keep the host decoders) and channel 0 is copied back.  TiffError for a file with fewer
     than ``level + 1`` levels."""
     p = TiffPyramid(path, samples=(1, 3, 4))
     if level >= p.level_count:
         raise TiffError(f"{path} has {p.level_count} levels, level {level} was asked for")
     lv = p.levels[level]
-    if lv.compression == 5 and _rocm_device_present():
+    if (lv.compression == 5 and _rocm_device_present()) or (lv.compression in (8, 32946) and deflate_level_on_device(lv) and _rocm_device_present("HIPAC_DEVICE_DEFLATE")):
         (dev, width), = p.to_device_levels("cuda", [level])
         return dev[:, :width, 0].contiguous().cpu().numpy()
     out = np.zeros((lv.height, lv.width), np.uint8)
@@ -607,18 +877,20 @@ def _split_jpeg_tables(data: bytes) -> Tuple[bytes, bytes]:
 def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, compression: str = "jpeg",
                      quality: int = 90, bigtiff: bool = False, missing: Sequence[Tuple[int, int, int]] = (),
                      jpeg_tables: bool = False, subsampling: int = -1, jpeg_options: Optional[dict] = None,
-                     predictor: int = 1, clear_when_full: bool = True):
+                     predictor: int = 1, clear_when_full: bool = True, deflate: Optional[Tuple[int, int]] = None):
     """Minimal writer of a tiled pyramid (tests and synthetic data only): ``levels`` are uint8[H,W,3]
     arrays, or uint8[H,W] for single-sample (grayscale, MinIsBlack) directories, largest first.  compression: "none" | "deflate" | "jpeg" (YCbCr; every tile a complete JPEG, or with
     ``jpeg_tables=True`` abbreviated streams plus one JPEGTables tag per directory, as real slide files have
     them).  ``missing``: (level, ty, tx) tiles written with byte count 0.  "lzw": ``lzw_encode`` streams, ``predictor`` 1 (tag 317
     absent) or 2 (horizontal differencing over the padded tile); uint8[H,W,4] levels (RGB + unassociated alpha) are
-    written with 4 samples for every compression but JPEG."""
+    written with 4 samples for every compression but JPEG.  ``deflate`` = (zlib level, zlib strategy) chooses the
+    blocks of "deflate" -- level 0 stored, ``zlib.Z_FIXED`` fixed Huffman, otherwise dynamic -- and admits ``predictor`` 2 with
+    it; None is ``zlib.compress(..., 6)`` without a predictor, exactly what the writer did before it knew the keyword."""
     from PIL import Image
 
     comp = {"none": 1, "deflate": 8, "jpeg": 7, "lzw": 5}[compression]
-    if predictor not in (1, 2) or (predictor == 2 and comp != 5):
-        raise TiffError("predictor 2 is written for LZW only")
+    if predictor not in (1, 2) or (predictor == 2 and comp != 5 and not (comp == 8 and deflate is not None)):
+        raise TiffError("predictor 2 is written for LZW, and for deflate when deflate=(level, strategy) is given")
     bo = "<"
     blobs, ifd_specs = [], []
     pos = 16 if bigtiff else 8
@@ -638,14 +910,18 @@ def write_tiled_tiff(path: str, levels: Sequence[np.ndarray], tile: int = 256, c
                 t[:part.shape[0], :part.shape[1]] = part
                 if comp == 1:
                     data = t.tobytes()
-                elif comp == 8:
-                    data = zlib.compress(t.tobytes(), 6)
-                elif comp == 5:
+                elif comp in (5, 8):
                     if predictor == 2:
                         d = t.reshape(tile, tile, -1).copy()
                         d[:, 1:] -= t.reshape(tile, tile, -1)[:, :-1]
                         t = d
-                    data = lzw_encode(t.tobytes(), clear_when_full)
+                    if comp == 5:
+                        data = lzw_encode(t.tobytes(), clear_when_full)
+                    elif deflate is None:
+                        data = zlib.compress(t.tobytes(), 6)
+                    else:
+                        z = zlib.compressobj(deflate[0], zlib.DEFLATED, 15, 8, deflate[1])
+                        data = z.compress(t.tobytes()) + z.flush()
                 else:
                     bio = io.BytesIO()
                     Image.fromarray(t, "L" if img.ndim == 2 else "RGB").save(bio, "JPEG", quality=quality, subsampling=subsampling, **(jpeg_options or {}))

@@ -1,8 +1,10 @@
 """Developer tool (GPU box): how fast a tiled pyramidal TIFF gets into HBM (tiff_pyramid.TiffPyramid.to_device_levels:
 tiles decoded on host threads, copied band by band) next to the scan of the same slide.
-usage: python tools/tiffbench.py [side] [compression: jpeg|deflate|none|lzw] [workers] [--compression lzw]
+usage: python tools/tiffbench.py [side] [compression: jpeg|deflate|none|lzw] [workers] [--compression lzw|deflate]
 With LZW the tool compares the device decoder (csrc/lzw.hip) with the host decoder on ``workers`` threads on the same file:
-median of 5 loads each, modes alternated (the writer's LZW encoder is plain Python: keep ``side`` small, default 2048)."""
+median of 5 loads each, modes alternated (the writer's LZW encoder is plain Python: keep ``side`` small, default 2048).
+``--compression deflate`` compares csrc/deflate.hip with zlib on ``workers`` threads in the same way (deflate as a positional
+argument times from_tiff and the scan, as before)."""
 import os
 import sys
 import tempfile
@@ -29,24 +31,25 @@ t = time.perf_counter()
 tiff_pyramid.write_tiled_tiff(path, levels, tile=512, compression=comp)
 print(f"wrote {path}: {os.path.getsize(path) / 1e6:.0f} MB in {time.perf_counter() - t:.1f} s")
 del l0, levels
-if comp == "lzw":
+if comp == "lzw" or flag == "deflate":
     import statistics
 
     times = {True: [], False: []}
     tp = tiff_pyramid.TiffPyramid(path)
     px = sum(w * h for w, h in tp.level_dimensions)
-    tp.to_device_levels("cuda", device_lzw=True)  # the first call loads the code object
+    switch = "device_lzw" if comp == "lzw" else "device_deflate"
+    tp.to_device_levels("cuda", **{switch: True})  # the first call loads the code object
     for rep in range(5):
         for on_device in (True, False):
             torch.cuda.synchronize()
             t = time.perf_counter()
-            out = tiff_pyramid.TiffPyramid(path).to_device_levels("cuda", workers=workers, device_lzw=on_device)
+            out = tiff_pyramid.TiffPyramid(path).to_device_levels("cuda", workers=workers, **{switch: on_device})
             torch.cuda.synchronize()
             times[on_device].append(time.perf_counter() - t)
             del out
     for on_device, name in ((True, "device"), (False, f"host, {workers} threads")):
         m = statistics.median(times[on_device])
-        print(f"to_device_levels (lzw, {name}): median of 5 {m:.3f} s = {px / 1e6 / m:.1f} Mpx/s  {[round(x, 3) for x in times[on_device]]}")
+        print(f"to_device_levels ({comp}, {name}): median of 5 {m:.3f} s = {px / 1e6 / m:.1f} Mpx/s  {[round(x, 3) for x in times[on_device]]}")
     sys.exit(0)
 for rep in range(2):
     t = time.perf_counter()
