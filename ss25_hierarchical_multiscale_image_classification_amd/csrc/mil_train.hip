@@ -20,6 +20,7 @@
 #include "common.h"
 
 #include "../../include/hipac_mil_train.h"
+#include "mil_train_internal.h"
 
 namespace hipac {
 
@@ -446,20 +447,14 @@ __global__ __launch_bounds__(256) void mt_l2_add_kernel(float* __restrict__ g, c
 
 }  // namespace hipac
 
-using namespace hipac;
+namespace hipac {
 
-extern "C" {
-
-int hipac_mil_train_abi_version(void) { return HIPAC_MIL_TRAIN_ABI_VERSION; }
-
-size_t hipac_mil_train_workspace_bytes(const hipac_mil_params_t* params, int pooling, int n, int n_bags) {
-  return mil_train_dims_ok(params, pooling, n, n_bags) ? make_mil_train_plan(params, pooling, n, n_bags).total : 0;
-}
-
-int hipac_mil_train_fwd_bwd(const hipac_mil_params_t* p, int pooling, const float* feats, int n_feat_rows, const int32_t* rows,
-                            const int32_t* bag_offsets, int n, int n_bags, const int64_t* labels, const float* class_w,
-                            const hipac_mil_params_t* grads, float* loss, float* logits, float* attn, void* workspace,
-                            size_t workspace_bytes, int accumulate, void* stream) {
+// The step itself.  `hook` (mil_train_internal.h) is called on hid after classifier.0 + ReLU and on dhid after
+// classifier.2's backward; hipac_mil_train_fwd_bwd passes none.
+int mil_train_run(const hipac_mil_params_t* p, int pooling, const float* feats, int n_feat_rows, const int32_t* rows,
+                  const int32_t* bag_offsets, int n, int n_bags, const int64_t* labels, const float* class_w,
+                  const hipac_mil_params_t* grads, float* loss, float* logits, float* attn, void* workspace, size_t workspace_bytes,
+                  int accumulate, void* stream, MilHiddenHook hook, void* hook_ctx) {
   HIPAC_REQUIRE(p && feats && bag_offsets && labels && grads && loss && logits && workspace, HIPAC_EINVAL,
                 "mil_train_fwd_bwd: null argument");
   HIPAC_REQUIRE(pooling >= HIPAC_MIL_ATTENTION && pooling <= HIPAC_MIL_MAX, HIPAC_EINVAL, "mil_train_fwd_bwd: pooling %d", pooling);
@@ -510,6 +505,7 @@ int hipac_mil_train_fwd_bwd(const hipac_mil_params_t* p, int pooling, const floa
   // classifier.0 + ReLU, classifier.2, cross-entropy, and their backward: hipac.h's entry points as they are
   int rc = hipac_linear_forward(pooled, p->fc1_w, p->fc1_b, hid, B, Hd, F, 1, stream);
   if (rc) return rc;
+  if (hook && (rc = hook(hid, B, Hd, hook_ctx, s))) return rc;
   rc = hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, B, Cn, Hd, 0, stream);
   if (rc) return rc;
   rc = hipac_cross_entropy_fwd_bwd(logits, labels, class_w, B, Cn, loss, dlogits, (float*)(ws + q.ce), stream);
@@ -517,6 +513,7 @@ int hipac_mil_train_fwd_bwd(const hipac_mil_params_t* p, int pooling, const floa
   rc = hipac_linear_backward(hid, p->fc2_w, dlogits, nullptr, nullptr, dhid, (float*)grads->fc2_w, (float*)grads->fc2_b, B, Cn, Hd,
                              accumulate, stream);
   if (rc) return rc;
+  if (hook && (rc = hook(dhid, B, Hd, hook_ctx, s))) return rc;
   rc = hipac_linear_backward(pooled, p->fc1_w, dhid, hid, dym, att ? g : nullptr, (float*)grads->fc1_w, (float*)grads->fc1_b, B, Hd,
                              F, accumulate, stream);
   if (rc) return rc;
@@ -542,6 +539,26 @@ int hipac_mil_train_fwd_bwd(const hipac_mil_params_t* p, int pooling, const floa
     HIPAC_CHECK_HIP(hipGetLastError());
   }
   return 0;
+}
+
+}  // namespace hipac
+
+using namespace hipac;
+
+extern "C" {
+
+int hipac_mil_train_abi_version(void) { return HIPAC_MIL_TRAIN_ABI_VERSION; }
+
+size_t hipac_mil_train_workspace_bytes(const hipac_mil_params_t* params, int pooling, int n, int n_bags) {
+  return mil_train_dims_ok(params, pooling, n, n_bags) ? make_mil_train_plan(params, pooling, n, n_bags).total : 0;
+}
+
+int hipac_mil_train_fwd_bwd(const hipac_mil_params_t* p, int pooling, const float* feats, int n_feat_rows, const int32_t* rows,
+                            const int32_t* bag_offsets, int n, int n_bags, const int64_t* labels, const float* class_w,
+                            const hipac_mil_params_t* grads, float* loss, float* logits, float* attn, void* workspace,
+                            size_t workspace_bytes, int accumulate, void* stream) {
+  return mil_train_run(p, pooling, feats, n_feat_rows, rows, bag_offsets, n, n_bags, labels, class_w, grads, loss, logits, attn,
+                       workspace, workspace_bytes, accumulate, stream, nullptr, nullptr);
 }
 
 int hipac_mil_train_l2_add(float* grads, const float* params, int64_t n, float wd, void* stream) {

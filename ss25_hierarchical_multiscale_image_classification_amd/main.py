@@ -130,6 +130,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mil_bag_size", type=int, default=None, help="sample at most this many patches per bag and epoch (default: the whole bag)")
     p.add_argument("--mil_bags_per_step", type=int, default=32)
     p.add_argument("--mil_model", type=str, default=os.path.join("models", "mil_model.pth"))
+    p.add_argument("--mil_dropout", type=float, default=0.0, metavar="P",
+                   help="dropout probability of the MIL head: on the feature rows and the classifier's hidden layer during --train_mil, "
+                        "and of the Monte-Carlo samples of --predict_mil (the reference's yaml: 0.5; default 0 = none); seeded by --seed")
+    p.add_argument("--mil_mc_samples", type=int, default=0, metavar="T",
+                   help="--predict_mil: also run T Monte-Carlo dropout forwards per bag -> results/mil_uncertainty.csv "
+                        "(the reference's yaml: 100; needs --mil_dropout > 0)")
+    p.add_argument("--mil_threshold", type=float, default=0.5, help="--mil_mc_samples: prediction = mean probability > this")
     p.add_argument("--detect", action="store_true",
                    help="write the detection CSVs --run_evaluation scores: dense scan of <data_root>/test/img at the levels of "
                         "--patch_level, probability map, smoothing and NMS on the device")
@@ -490,6 +497,16 @@ def cmd_mil(args, train: bool):
     triple = mil_triple(args)  # before anything touches a GPU
     if triple is None:
         return 2
+    if not 0.0 <= args.mil_dropout < 1.0:
+        print(f"[ERROR] --mil_dropout {args.mil_dropout}: the probability must satisfy 0 <= P < 1.")
+        return 2
+    if not train and args.mil_mc_samples != 0:
+        if not 0 < args.mil_mc_samples <= 4096:
+            print(f"[ERROR] --mil_mc_samples {args.mil_mc_samples}: give 1 .. 4096 samples.")
+            return 2
+        if args.mil_dropout == 0.0:
+            print("[ERROR] --mil_mc_samples needs --mil_dropout P with 0 < P < 1: without dropout every sample is the same forward.")
+            return 2
     from .dist import rank_world
 
     if rank_world()[0] != 0:  # not sharded: rank 0 does it
@@ -499,12 +516,13 @@ def cmd_mil(args, train: bool):
     if train:
         mil_train.train_mil(*triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, epochs=args.mil_epochs,
                             bags_per_step=args.mil_bags_per_step, bag_size=args.mil_bag_size,
-                            seed=0 if args.seed is None else args.seed, max_steps=args.max_steps)
+                            seed=0 if args.seed is None else args.seed, max_steps=args.max_steps, dropout=args.mil_dropout)
         return 0
     if not os.path.exists(args.mil_model):
         print(f"[ERROR] {args.mil_model} not found: run --train_mil first or give --mil_model PATH.")
         return 2
-    mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide)
+    mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, dropout=args.mil_dropout,
+                          mc_samples=args.mil_mc_samples, threshold=args.mil_threshold, seed=0 if args.seed is None else args.seed)
     return 0
 
 

@@ -4,7 +4,8 @@
   constructor arguments, ``forward(bag) -> (logits, attention)`` shapes and state_dict keys
   (``aggregator.attn_V.*``, ``aggregator.attn_U.*``, ``classifier.0.*``, ``classifier.2.*``).
   In ``eval()`` mode ``forward`` runs ``hipac_mil_forward`` (HIP) -- a CPU tensor raises, there is
-  no CPU fallback; in ``train()`` mode it runs the ordinary autograd graph.
+  no CPU fallback; in ``train()`` mode it runs the ordinary autograd graph, under the dropout masks of
+  ``mil_dropout.host_mask`` when ``dropout > 0`` (applied functionally: no module, no new state_dict key).
   ``forward_bags`` scores MANY bags in one launch pair (the reference loops over bags).
 * ``group_patches_by_wsi`` / ``WSIMILDDataset`` -- src/datasets/mildataset.py:6-47.  By default the
   bag key is the reference's as written: ``'_'.join(basename.split('_')[:-2])``, which for the patch
@@ -81,11 +82,16 @@ class MILAttentionPooling(nn.Module):
 class MILClassifier(nn.Module):
     """mil_classifier.py:20-45."""
 
-    def __init__(self, feature_dim, num_classes=2, pooling="attention"):
+    def __init__(self, feature_dim, num_classes=2, pooling="attention", dropout=0.0, dropout_seed=0):
         super().__init__()
         if pooling not in ("attention", "mean", "max"):
             raise ValueError("Unknown pooling: choose from 'attention', 'mean', 'max'")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError("dropout must satisfy 0 <= p < 1")
         self.pooling = pooling
+        # plain attributes, not parameters or buffers: the state_dict keeps the reference's keys.  dropout_step is the
+        # mask's sample index (the trainer's step number); the caller advances it.
+        self.dropout, self.dropout_seed, self.dropout_step = float(dropout), int(dropout_seed), 0
         if pooling == "attention":
             self.aggregator = MILAttentionPooling(feature_dim)
         self.classifier = nn.Sequential(nn.Linear(feature_dim, 128), nn.ReLU(), nn.Linear(128, num_classes))
@@ -103,9 +109,18 @@ class MILClassifier(nn.Module):
         logits, attn, pooled = capi.mil_forward(sd, self.pooling, feats.contiguous(), offs, want_pooled=want_pooled)
         return (logits, attn, pooled) if want_pooled else (logits, attn)
 
-    def forward(self, bag):
-        """bag: (num_patches, feature_dim) -> (logits (num_classes), attention (num_patches, 1) or None)."""
+    def forward(self, bag, row0=0, bag_index=0):
+        """bag: (num_patches, feature_dim) -> (logits (num_classes), attention (num_patches, 1) or None).  ``row0`` (the
+        position of the bag's first row in the batch) and ``bag_index`` place the bag in the dropout masks; they matter in
+        ``train()`` mode with ``dropout > 0`` only."""
         if self.training:
+            if self.dropout > 0.0:
+                from .mil_dropout import host_dropout
+
+                p, seed, step = self.dropout, self.dropout_seed, self.dropout_step
+                pooled, attn = self._aggregate(host_dropout(bag, p, seed, step, 0, row0))
+                hid = host_dropout(self.classifier[1](self.classifier[0](pooled)), p, seed, step, 1, bag_index)
+                return self.classifier[2](hid), attn
             pooled, attn = self._aggregate(bag)
             return self.classifier(pooled), attn
         logits, attn = self.forward_bags(bag, torch.tensor([0, bag.shape[0]]))

@@ -10,6 +10,9 @@ decay 1e-4, 50 epochs, 32 bags per step, early stopping with patience 5, a 0.8 /
   rows of the resident feature matrix, the L2 term, ``hipac_adam_step``.
 * ``train_mil`` / ``predict_mil``: the loop and the scoring over the (features, labels, paths) triple that
   ``--extract_features`` writes.  Validation and prediction go through ``MILClassifier.forward_bags``.
+* Dropout (the yaml's ``dropout_rate``) and Monte-Carlo dropout uncertainty (its ``uncertainty_estimation``) come from
+  ``mil_dropout.py``: the trainer's step under ``hipac_mil_dropout_train_fwd_bwd``, ``predict_mil``'s
+  ``results/mil_uncertainty.csv`` from ``mil_dropout.mc_forward``.
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, mil_dropout
 from .mil import MILClassifier, group_patches_by_wsi
 from .train_native import FlatAdam
 
@@ -60,13 +63,17 @@ PARAM_FIELDS = (("aggregator.attn_V.weight", "attn_V_w"), ("aggregator.attn_V.bi
 class NativeMILTrainer:
     """``MILClassifier`` under torch.optim.Adam(lr, weight_decay) with the whole step in HIP.  ``sd``: a MILClassifier
     state_dict (any device, converted to float32); the parameters live in one flat buffer, every tensor starting on a
-    16-byte boundary (the gaps stay 0)."""
+    16-byte boundary (the gaps stay 0).  ``dropout`` > 0: every forward_backward runs under the masks of
+    (``seed``, sample = the number of steps taken so far) -- include/hipac_mil_dropout.h; 0 is the step as it always was."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], pooling: str, device, lr: float = 1e-3, weight_decay: float = 1e-4,
-                 class_weights=None):
+                 class_weights=None, dropout: float = 0.0, seed: int = 0):
         if pooling not in capi.MIL_POOLING:
             raise ValueError("Unknown pooling: choose from 'attention', 'mean', 'max'")
         self.lib = load_mil_train_library()
+        self.dropout, self.seed, self.steps = mil_dropout.check_p(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        if self.dropout > 0.0:
+            mil_dropout.load_mil_dropout_library()
         self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
         if self.device.type != "cuda":
             raise capi.HipacError("NativeMILTrainer needs a ROCm device: there is no CPU fallback")
@@ -156,7 +163,8 @@ class NativeMILTrainer:
         lab = lab.to(self.device).contiguous()
         offs_dev = torch.from_numpy(offs.astype(np.int32)).to(self.device)
         pool = capi.MIL_POOLING[self.pooling]
-        need = self.lib.hipac_mil_train_workspace_bytes(C.addressof(self._p), pool, n, n_bags)
+        query = self.lib.hipac_mil_dropout_train_workspace_bytes if self.dropout > 0.0 else self.lib.hipac_mil_train_workspace_bytes
+        need = query(C.addressof(self._p), pool, n, n_bags)
         if need == 0:
             raise capi.HipacError(f"mil training step of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
         if self._ws is None or self._ws.numel() < need:
@@ -164,12 +172,15 @@ class NativeMILTrainer:
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         logits = torch.empty((n_bags, self.C), dtype=torch.float32, device=self.device)
         self.attn = torch.empty(n, dtype=torch.float32, device=self.device) if (want_attn and self.pooling == "attention") else None
-        with torch.cuda.device(self.device):
-            rc = self.lib.hipac_mil_train_fwd_bwd(
-                C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
+        args = (C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
                 lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
-                capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0, capi._stream())
-        capi._check(rc, "hipac_mil_train_fwd_bwd")
+                capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0)
+        with torch.cuda.device(self.device):
+            if self.dropout > 0.0:
+                rc = self.lib.hipac_mil_dropout_train_fwd_bwd(*args, self.dropout, self.seed, self.steps & 0xFFFFFFFF, capi._stream())
+            else:
+                rc = self.lib.hipac_mil_train_fwd_bwd(*args, capi._stream())
+        capi._check(rc, "hipac_mil_dropout_train_fwd_bwd" if self.dropout > 0.0 else "hipac_mil_train_fwd_bwd")
         return loss, logits
 
     def step(self, feats, rows, offsets, labels) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -181,6 +192,7 @@ class NativeMILTrainer:
                                                             self.opt.params.numel(), self.weight_decay, capi._stream()),
                             "hipac_mil_train_l2_add")
         self.opt.step()
+        self.steps += 1
         return loss, logits
 
 
@@ -269,9 +281,13 @@ def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray) -> torch.Tensor:
 
 def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False, epochs: int = 50,
               bags_per_step: int = 32, bag_size: Optional[int] = None, lr: float = 1e-3, weight_decay: float = 1e-4,
-              patience: int = 5, seed: int = 0, out_dir: str = ".", max_steps: Optional[int] = None, device=None) -> Dict[str, object]:
+              patience: int = 5, seed: int = 0, out_dir: str = ".", max_steps: Optional[int] = None, device=None,
+              dropout: float = 0.0) -> Dict[str, object]:
     """The yaml's loop (module docstring).  Writes ``<out_dir>/models/mil_model.pth`` (the state with the best validation
-    loss; the last one when there is no validation split) and ``<out_dir>/results/metrics.json``; returns the metrics."""
+    loss; the last one when there is no validation split) and ``<out_dir>/results/metrics.json``; returns the metrics.
+    ``dropout`` > 0 trains under dropout (masks seeded by ``seed``); validation and test scoring stay deterministic, and
+    the metrics then carry a ``"dropout"`` key."""
+    dropout = mil_dropout.check_p(dropout)
     feats, order, offsets, names, wsi = load_triple(features_path, labels_path, paths_path, by_slide)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     tr, va, te = split_bags(len(names), seed)
@@ -279,7 +295,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
     if len(va) == 0:
         print("[INFO] MIL: the validation split is empty: early stopping is off")
     feats_dev = torch.from_numpy(feats).to(dev)  # uploaded once; every step reads it in place through a row index
-    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed), pooling, dev, lr=lr, weight_decay=weight_decay)
+    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed), pooling, dev, lr=lr, weight_decay=weight_decay,
+                               dropout=dropout, seed=seed)
     labels_all = torch.from_numpy(wsi)
     val = _gathered(feats_dev, va, order, offsets) if len(va) else None
     val_labels = labels_all[torch.from_numpy(va)].to(dev) if len(va) else None
@@ -326,6 +343,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
     metrics.update({"train_loss": history["train_loss"], "val_loss": history["val_loss"], "epochs_run": len(history["train_loss"]),
                     "steps": steps, "early_stopped": stopped, "pooling": pooling,
                     "split_sizes": {"train": int(len(tr)), "val": int(len(va)), "test": int(len(te))}})
+    if dropout > 0.0:
+        metrics["dropout"] = dropout
     with open(os.path.join(out_dir, "results", "metrics.json"), "w") as f:
         json.dump(metrics, f, indent=2)
     print(f"[INFO] MIL: model saved to {model_path}; test accuracy {metrics['accuracy']:.4f}")
@@ -333,9 +352,19 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
 
 
 def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False,
-                out_dir: str = ".", device=None) -> List[Tuple[str, float, int]]:
+                out_dir: str = ".", device=None, dropout: float = 0.0, mc_samples: int = 0, threshold: float = 0.5, seed: int = 0
+                ) -> List[Tuple[str, float, int]]:
     """Every bag of the triple scored with a saved model -> [(bag name, probability of class 1, predicted label)], also
-    written as ``<out_dir>/results/mil_predictions.csv``."""
+    written as ``<out_dir>/results/mil_predictions.csv``.  With ``mc_samples`` > 0 (needs ``dropout`` > 0) it also writes
+    ``<out_dir>/results/mil_uncertainty.csv``: per bag the mean and the variance (divisor T - 1, ``torch.var``) of the
+    class-1 probability over ``mc_samples`` stochastic forwards, the entropy of the mean, the mean entropy, their difference
+    (the mutual information), and ``mean_probability > threshold`` (the reference's ``softmax_thresholding``)."""
+    dropout, mc_samples = mil_dropout.check_p(dropout), int(mc_samples)
+    if mc_samples < 0 or mc_samples > mil_dropout.MC_MAX_SAMPLES:
+        raise ValueError(f"mc_samples must be in 0..{mil_dropout.MC_MAX_SAMPLES}, got {mc_samples}")
+    if mc_samples > 0 and dropout == 0.0:
+        raise ValueError("Monte-Carlo dropout needs a dropout probability: give --mil_dropout P with 0 < P < 1 "
+                         "(with P = 0 every sample is the same forward)")
     feats, order, offsets, names, _ = load_triple(features_path, labels_path, paths_path, by_slide)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     sd = {k: v.to(dev, torch.float32).contiguous() for k, v in torch.load(model_path, map_location="cpu", weights_only=True).items()}
@@ -351,4 +380,16 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
         for n, p, y in out:
             fh.write(f"{n},{p:.6f},{y}\n")
     print(f"[INFO] MIL: {len(out)} bags scored -> {os.path.join(out_dir, 'results', 'mil_predictions.csv')}")
+    if mc_samples > 0:
+        if int(sd["classifier.2.weight"].shape[0]) < 2:
+            raise ValueError("the uncertainty table reports class 1: the model needs at least two classes")
+        mc = mil_dropout.mc_forward(sd, pooling, f, offs, dropout, seed, mc_samples)
+        cols = [mc["mean_prob"][:, 1], mc["var_prob"][:, 1], mc["entropy"], mc["expected_entropy"], mc["mutual_info"]]
+        table = torch.stack(cols, dim=1).cpu().numpy()
+        path = os.path.join(out_dir, "results", "mil_uncertainty.csv")
+        with open(path, "w") as fh:
+            fh.write("bag,mean_probability,variance,entropy,expected_entropy,mutual_information,prediction\n")
+            for name, row in zip(names, table):
+                fh.write(f"{name},{row[0]:.6f},{row[1]:.6e},{row[2]:.6f},{row[3]:.6f},{row[4]:.6f},{int(row[0] > threshold)}\n")
+        print(f"[INFO] MIL: {mc_samples} Monte-Carlo dropout samples (p = {dropout}) -> {path}")
     return out
