@@ -57,9 +57,11 @@ extern "C" {
                                relative per term): meets the reference's fp32 results (src/main.py:870) to 1e-3.
                                NHWC4_PAD input is float32[B,230,232,4] in this mode. */
 #define HIPAC_PREC_FP16Q8 4 /* the faster parity mode: the pair layout of FP16X3, hi*hi on the fp16 MFMA and the two cross
-                               products hi*lo + lo*hi of the 3x3 / stride 1 convolutions on the e4m3 MX MFMA with constant
-                               scales (2 MFMA time units per term instead of 3): logits within ~5e-5 of the reference's fp32
-                               results, labels identical.  Inputs as for FP16X3. */
+                               products hi*lo + lo*hi of the 3x3 convolutions on the e4m3 MX MFMA (2 MFMA time units per term
+                               instead of 3).  The e4m3 scales are constants on the activation side; every conv's weights (both
+                               pair modes) are packed times their own power of two 2^S, which the kernel undoes exactly, so the
+                               weights' magnitude does not matter: logits within ~5e-5 of the reference's fp32 results, labels
+                               identical.  Inputs as for FP16X3. */
 
 /* input layouts accepted by hipac_resnet18_forward */
 #define HIPAC_IN_NCHW_F32 0   /* float32[B,3,224,224], the reference's layout (src/main.py:870) */

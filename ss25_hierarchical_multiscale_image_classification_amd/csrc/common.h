@@ -92,14 +92,17 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 // precision fp16q8 (halo16x2.h): the constant power-of-two scales of the e4m3 byte planes.  Activations: hi8 = e4m3(hi), lo8 = e4m3(lo * 2^11);
-// weights (resnet_pack.hip, pack_conv_pairs): whi8 = e4m3(whi * 2^4), wlo8 = e4m3(wlo * 2^15).  Both cross products carry 2^(11 + 4) = 2^(0 + 15).
-constexpr int kQ8LoShift = 11, kQ8WhiShift = 4, kQ8WloShift = 15;
+// weights (resnet_pack.hip, pack_conv_pairs): (whi, wlo) = the pair of w * 2^S, S per conv such that max |w| 2^S is in [2^12, 2^13] (ConvW::wscale);
+// whi8 = e4m3(whi * 2^-5) (<= 256), wlo8 = e4m3(wlo * 2^6) (|wlo| <= 4: <= 256).  Both cross products carry 2^(11 - 5) = 2^(0 + 6).
+constexpr int kQ8LoShift = 11, kQ8WhiShift = -5, kQ8WloShift = 6;
+constexpr int kPairShiftMax = 15;  // S <= 15: 2^S is the entry of the residual pass's fp16 identity matrix (halo16x2.h)
 static_assert(kQ8LoShift + kQ8WhiShift == kQ8WloShift, "one scale for both cross products");
 
 // ---- packed network description shared by the TUs ---------------------------------
 struct ConvW {
   void* w;      // device, T[Cout][K] (K = kh*kw*Cin, or 7*32 for the stem)
   float* bias;  // device, float[Cout]
+  float wscale, winv;  // pair modes' convs (pack_conv_pairs): the weights are packed times wscale = 2^S, winv = 2^-S; 1 elsewhere
 };
 
 struct Net {

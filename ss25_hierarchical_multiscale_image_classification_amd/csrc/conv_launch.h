@@ -224,7 +224,7 @@ static int launch_halo16x2(const void* in, const void* in_q, const ConvW& w, con
   const TileGrid g = tile_grid(M, BM, COUT / BN, HIPAC_HALO_GRID);
   return launch_dyn_lds<kern>(g.blocks, 256, LDS, s, (const _Float16*)in, (const unsigned char*)in_q, (const unsigned char*)w.w,
                               bias ? bias : w.bias, (const _Float16*)resid, out, (unsigned char*)out_q, M, n, g.n_mtiles,
-                              (const unsigned char*)resid_q, (const unsigned char*)wgt_p);
+                              (const unsigned char*)resid_q, (const unsigned char*)wgt_p, w.wscale, w.winv);
 }
 // the two pair modes' convs through one call: MODE 1 = fp16q8 (byte tensors, flags as given), MODE 2 = fp16x3 on the same kernel (pairs
 // only: no q8 output, the lo plane always written)

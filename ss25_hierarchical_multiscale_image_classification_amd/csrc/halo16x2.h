@@ -10,9 +10,16 @@
 // v_mfma_scale_f32_16x16x128_f8f6f4 with OCP e4m3 operands (measured, tools/mfma_f8_probe.hip: 2.25x the FLOP/s of the f16
 // instruction on random data under the power cap), with CONSTANT scales (tests/tools/prec_mx.py: e4m3's own exponent gives every
 // element its dynamic range; logits 5e-5 against the fp32 oracle where fp16x3 has 4e-6 and one fp16 product 1e-3):
-//     activations:  hi8 = e4m3(xhi),  lo8 = e4m3(xlo * 2^11)        weights:  whi8 = e4m3(whi * 2^4),  wlo8 = e4m3(wlo * 2^15)
-// so both cross products carry the factor 2^15, which the instruction's E8M0 scale operand (2^-15 on the weight side, 2^0 on the
+//     activations:  hi8 = e4m3(xhi),  lo8 = e4m3(xlo * 2^11)        weights:  whi8 = e4m3(whi * 2^-5),  wlo8 = e4m3(wlo * 2^6)
+// so both cross products carry the factor 2^6, which the instruction's E8M0 scale operand (2^-6 on the weight side, 2^0 on the
 // activation side) removes on the way into the SAME fp32 accumulators the f16 products go to.
+//
+// Weight scale (both modes).  (whi, wlo) is the pair of w 2^S, not of w: resnet_pack.hip (pack_conv_pairs) scales each conv's folded
+// weights by its own power of two so that the largest sits in [2^12, 2^13] -- the lo halves are then normal fp16 numbers whatever the
+// checkpoint's magnitudes are (unscaled, lo = 2^-11 w is an fp16 subnormal for every |w| < 0.125), and the e4m3 windows above sit where
+// the weights are.  The accumulators therefore hold 2^S times the conv's sums; all of it is exact: a folded projection (PCIN) shares its
+// conv's S, the residual pass adds 2^S I x R (`wscale` = 2^S <= 2^15 is an fp16 number), and every epilogue forms acc * 2^-S + bias in
+// ONE fused multiply-add (`winv` = 2^-S) where it used to add the bias -- no instruction more.
 //
 // Layout.  Activations are the fp16x3 pair tensor [pixel][hi: C | lo: C] (what the residual adds and the other kernels of the
 // mode read and write) PLUS a byte tensor q8 [pixel][C / 64][lo8: 64 | hi8: 64]: per 64-channel chunk one 128-byte row -- the
@@ -71,7 +78,7 @@ __device__ __forceinline__ unsigned cvt4_e4m3(float a, float b, float c, float d
 __device__ inline unsigned cvt4_e4m3(float, float, float, float) { return 0; }
 #endif
 constexpr float kQ8LoScale = (float)(1 << kQ8LoShift);  // activations' lo parts are converted as lo * 2^11 (common.h has the shifts)
-constexpr int kQ8ScaleA = 127 - kQ8WloShift, kQ8ScaleB = 127;  // E8M0 scale operands of the MFMA: 2^-15 on the weight side
+constexpr int kQ8ScaleA = 127 - kQ8WloShift, kQ8ScaleB = 127;  // E8M0 scale operands of the MFMA: 2^-6 on the weight side
 
 // pair tensor -> q8 tensor, for the activations the mode's other kernels produce (stem + pool, the stride-2 entry convs)
 template <int UNUSED = 0>  // (a template: the header is part of several translation units)
@@ -100,6 +107,7 @@ static int launch_pairs_to_q8(const void* in, void* q, long long n_pix, int C, h
   return (int)hipGetLastError();
 }
 
+// wscale = 2^S, winv = 2^-S: the power of two the conv's (and its folded projection's) weights were packed with (ConvW).
 // Q8OUT: also write the q8 tensor of the output (for a following conv of this kind).  POOL: the network's last conv -- the pooled
 // fp32 epilogue of halo16.h (partial sums in `outp`), no pair / q8 output.  OUTF32: the fp32 map float[pixel][COUT] instead of pairs.
 // BN: 128 (waves 2 x 2, each 128 px x 64 ch) or 64 (layer1: waves 4 x 1, each 64 px x 64 ch).
@@ -121,7 +129,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
                                                                   const _Float16* __restrict__ resid, void* __restrict__ outp,
                                                                   unsigned char* __restrict__ out_q, int M, int n_img, int n_mtiles,
                                                                   const unsigned char* __restrict__ resid_q = nullptr,
-                                                                  const unsigned char* __restrict__ wgt_p = nullptr) {
+                                                                  const unsigned char* __restrict__ wgt_p = nullptr, float wscale = 1.f,
+                                                                  float winv = 1.f) {
   using T = _Float16;
   using frag = f16x8;
   constexpr int BM = 256;
@@ -507,7 +516,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
 #pragma unroll
     for (int o = 0; o < 2; ++o)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) ident[o][e] = (g == 2 * o + (n16 >> 3) && e == (n16 & 7)) ? (T)1.0f : (T)0.0f;
+      for (int e = 0; e < 8; ++e) ident[o][e] = (g == 2 * o + (n16 >> 3) && e == (n16 & 7)) ? (T)wscale : (T)0.0f;  // 2^S I: the sums are 2^S too large
     const int r0 = wm * WPX + pn;  // slot of sub-tile 0's pixel
     const unsigned rb0 = lds0 + (unsigned)((wn ? Wbuf : Abuf) - ring) + (unsigned)(r0 * 128 + ((g ^ ((r0 >> 1) & 7)) << 4));
     // (BN = 64 with a 32 KB ring: both planes in ONE round trip, the hi tile into the band region, the lo tile into the ring)
@@ -599,7 +608,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
       const bool live = m < M;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
+        float v[4] = {__builtin_fmaf(acc[i][j][0], winv, bv[j].x), __builtin_fmaf(acc[i][j][1], winv, bv[j].y),
+                      __builtin_fmaf(acc[i][j][2], winv, bv[j].z), __builtin_fmaf(acc[i][j][3], winv, bv[j].w)};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           v[e] = live ? fmaxf(v[e], 0.f) : 0.f;
@@ -629,7 +639,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
     } else if constexpr (OUTF32) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        float v[4] = {acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y, acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w};
+        float v[4] = {__builtin_fmaf(acc[i][j][0], winv, bv[j].x), __builtin_fmaf(acc[i][j][1], winv, bv[j].y),
+                      __builtin_fmaf(acc[i][j][2], winv, bv[j].z), __builtin_fmaf(acc[i][j][3], winv, bv[j].w)};
         if constexpr (RELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
@@ -654,7 +665,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
         int q_h = 0, q_l = 0;
         static_for<2>([&](auto HP) {
           constexpr int hp = decltype(HP)::value;
-          const f32x2 u = f32x2{acc[i][j][2 * hp], acc[i][j][2 * hp + 1]} + bb[hp];
+          const f32x2 u = __builtin_elementwise_fma(f32x2{acc[i][j][2 * hp], acc[i][j][2 * hp + 1]}, f32x2{winv, winv}, bb[hp]);
           f32x2 v = u;
           if constexpr (RELU) v = f32x2{fmaxf(u[0], 0.f), fmaxf(u[1], 0.f)};
           const f16x2 h2 = __builtin_convertvector(v, f16x2);

@@ -58,6 +58,7 @@ static int upload(const void* host, size_t bytes, void** dev) {
   return 0;
 }
 static int upload_convw(const void* w, size_t w_bytes, const std::vector<float>& bias, ConvW* out) {
+  out->wscale = out->winv = 1.f;
   const int rc = upload(w, w_bytes, &out->w);
   return rc ? rc : upload(bias.data(), bias.size() * 4, (void**)&out->bias);
 }
@@ -89,9 +90,27 @@ static int pack_conv(const hipac_convbn_t& c, int cout, int cin, int ks, float e
 
 // The pair modes' convs (halo16x2.h; taps = 9: 3x3, taps = 1: projection): BN folded, every weight split into the fp16 pair
 // (hi, lo); per output channel and tap, per 64-channel chunk 256 bytes:
-//   q8 (fp16q8):      [hi: 64 fp16 | e4m3(hi * 2^4): 64 | e4m3(lo * 2^15): 64]
+//   q8 (fp16q8):      [hi: 64 fp16 | e4m3(hi * 2^-5): 64 | e4m3(lo * 2^6): 64]
 //   !q8 (fp16x3):     [hi: 64 fp16 | lo: 64 fp16]
-static int pack_conv_pairs(const hipac_convbn_t& c, int cout, int cin, int taps, float eps, bool q8, ConvW* out) {
+// (hi, lo) is the pair of w * 2^S (exact), S = pair_shift of the conv -- as pack_stem_u8 does it and for its reason: unscaled,
+// lo ~ 2^-11 w is an fp16 subnormal for every |w| < 0.125 and carries the fewer bits the smaller the weight is, and the e4m3 rows
+// have one fixed window.  The kernel's epilogue multiplies the accumulator by 2^-S (ConvW::winv; halo16x2.h).
+static double folded_absmax(const hipac_convbn_t& c, int cout, int cin, int taps, float eps) {
+  if (!(c.conv_w && c.bn_gamma && c.bn_beta && c.bn_mean && c.bn_var)) return 0.0;  // (pack_conv_pairs reports it)
+  double wmax = 0.0;
+  for (int o = 0; o < cout; ++o) {
+    const double scale = bn_fold(c, o, eps).scale;
+    for (size_t k = 0; k < (size_t)cin * taps; ++k) wmax = fmax(wmax, fabs((double)c.conv_w[(size_t)o * cin * taps + k] * scale));
+  }
+  return wmax;
+}
+// S = floor(log2(2^13 / max |w|)), clamped to [0, kPairShiftMax]: the largest scaled weight in [2^12, 2^13]
+static int pair_shift(double wmax) {
+  if (!(wmax > 0.0) || !(wmax < HUGE_VAL)) return 0;
+  const int S = (int)floor(log2(8192.0 / wmax));
+  return S < 0 ? 0 : (S > kPairShiftMax ? kPairShiftMax : S);
+}
+static int pack_conv_pairs(const hipac_convbn_t& c, int cout, int cin, int taps, float eps, bool q8, int S, ConvW* out) {
   HIPAC_REQUIRE(c.conv_w && c.bn_gamma && c.bn_beta && c.bn_mean && c.bn_var, HIPAC_EINVAL,
                 "pack: null tensor pointer (cout=%d cin=%d q8)", cout, cin);
   HIPAC_REQUIRE(cin % 64 == 0, HIPAC_EINVAL, "pack: q8 layout needs cin %% 64 == 0 (%d)", cin);
@@ -103,7 +122,7 @@ static int pack_conv_pairs(const hipac_convbn_t& c, int cout, int cin, int taps,
     bias[o] = (float)bn.bias;
     for (int i = 0; i < cin; ++i)
       for (int tap = 0; tap < taps; ++tap) {
-        const float v = (float)((double)c.conv_w[((size_t)o * cin + i) * taps + tap] * bn.scale);
+        const float v = (float)ldexp((double)c.conv_w[((size_t)o * cin + i) * taps + tap] * bn.scale, S);
         const uint16_t hb = f32_to_f16_bits(v);
         const float hi = f16_bits_to_f32(hb);
         const uint16_t lb = f32_to_f16_bits(v - hi);
@@ -117,7 +136,9 @@ static int pack_conv_pairs(const hipac_convbn_t& c, int cout, int cin, int taps,
         }
       }
   }
-  return upload_convw(w.data(), w.size(), bias, out);
+  const int rc = upload_convw(w.data(), w.size(), bias, out);
+  out->wscale = ldexpf(1.f, S), out->winv = ldexpf(1.f, -S);
+  return rc;
 }
 
 // Stem weights for the strip kernel (uint8 input, stem.h: stem_pool_strip2_kernel): BN folded as in
@@ -214,19 +235,27 @@ static int pack_net(const hipac_resnet18_params_t& params, int precision, Net& n
   // packed as halo16x2.h's weight rows -- fp16q8 with e4m3 rows, fp16x3 with the lo halves as fp16.
   PACK_TRY(pack_conv(params.stem, 64, 3, 7, eps, split ? HIPAC_PREC_FP32 : precision, true, &net.stem));
   if (precision != HIPAC_PREC_FP32) PACK_TRY(pack_stem_u8(params.stem, eps, precision, &net.stem_u8));
-  auto pack = [&](const hipac_convbn_t& c, int cout, int cin, int ks, ConvW* out) {
-    return split ? pack_conv_pairs(c, cout, cin, ks * ks, eps, q8, out)
-                 : pack_conv(c, cout, cin, ks, eps, precision, false, out);
+  // pair modes: S < 0 = the conv's own power-of-two weight scale
+  auto pack = [&](const hipac_convbn_t& c, int cout, int cin, int ks, ConvW* out, int S = -1) {
+    if (!split) return pack_conv(c, cout, cin, ks, eps, precision, false, out);
+    return pack_conv_pairs(c, cout, cin, ks * ks, eps, q8, S < 0 ? pair_shift(folded_absmax(c, cout, cin, ks * ks, eps)) : S, out);
   };
   const int ch[4] = {64, 128, 256, 512};
+  int S_proj[3] = {-1, -1, -1};
   for (int s = 0; s < 4; ++s)
     for (int b = 0; b < 2; ++b)
       for (int k = 0; k < 2; ++k) {
         const int cin = s > 0 && b == 0 && k == 0 ? ch[s - 1] : ch[s];  // the stage's entry conv widens
-        PACK_TRY(pack(params.block[2 * s + b][k], ch[s], cin, 3, &net.block[2 * s + b][k]));
+        int S = -1;
+        if (split && s > 0 && b == 0 && k == 1) {
+          // the projection is folded into this conv (halo16x2.h, PCIN) and shares its accumulator: one S for the two
+          const double wmax = fmax(folded_absmax(params.block[2 * s][1], ch[s], ch[s], 9, eps), folded_absmax(params.down[s - 1], ch[s], ch[s - 1], 1, eps));
+          S = S_proj[s - 1] = pair_shift(wmax);
+        }
+        PACK_TRY(pack(params.block[2 * s + b][k], ch[s], cin, 3, &net.block[2 * s + b][k], S));
       }
   for (int s = 1; s < 4; ++s)  // (pair modes: folded into conv2, halo16x2.h, PCIN)
-    PACK_TRY(pack(params.down[s - 1], ch[s], ch[s - 1], 1, &net.down[s - 1]));
+    PACK_TRY(pack(params.down[s - 1], ch[s], ch[s - 1], 1, &net.down[s - 1], S_proj[s - 1]));
   for (int s = 1; s < 4 && precision != HIPAC_PREC_FP32; ++s) {
     // block0.conv2's bias + the projection's, for the kernel that accumulates both into one accumulator
     std::vector<float> bs(ch[s]);

@@ -2,7 +2,16 @@
 the product hi*hi stays on the fp16 MFMA, and the two cross terms hi*lo + lo*hi run on the block-scaled MX MFMA
 (v_mfma_scale_f32_32x32x64_f8f6f4: one E8M0 scale per 32 K-elements) with e4m3 (2x the fp16 rate) or e2m3 (4x) operands.
 Prints the error of features / logits against the fp32 oracle for: fp16x3 (exact cross terms), MXFP8 and MXFP6 cross
-terms, and the single fp16 product.  usage: python tests/tools/prec_mx.py [n_patches]"""
+terms, and the single fp16 product.
+
+The pair weights are emulated as resnet_pack.hip (pack_conv_pairs) packs them: per conv the folded weights times 2^S,
+S = floor(log2(2^13 / max|w|)) clamped to [0, 15] (a folded projection shares its conv's S), split into (hi, lo), the e4m3 rows
+e4m3(hi * 2^-5) and e4m3(lo * 2^6), the sum times 2^-S.  --no-wscale gives the former packing (no scale, e4m3(hi * 2^4),
+e4m3(lo * 2^15)).  --rescale K applies tests/rescale_cases.py's function-preserving channel rescaling (2^+-K) to the state dict
+first: the oracle's results do not move, the emulated modes' errors do.
+usage: python tests/tools/prec_mx.py [n_patches] [--rescale K] [--no-wscale]"""
+import argparse
+import math
 import os
 import sys
 
@@ -10,6 +19,8 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rescale_cases  # noqa: E402
 from oracle import resnet18_ref as R, transform_ref as T  # noqa: E402
 from ss25_hierarchical_multiscale_image_classification_amd import synth  # noqa: E402
 
@@ -58,23 +69,33 @@ def const_quant(v, shift):
     return (v * 2.0 ** shift).clamp(-448, 448).to(torch.float8_e4m3fn).float() / 2.0 ** shift
 
 
-def conv3(x, w, b, fmt, mode, **kw):
-    """One convolution in the emulated arithmetic.  mode: 'x3' three products, 'x1' single fp16 product."""
+def pair_shift(*ws):
+    """pack_conv_pairs' S of a conv (and the projection folded into it): the largest scaled weight in [2^12, 2^13]."""
+    wmax = max(float(w.abs().max()) for w in ws)
+    return min(max(math.floor(math.log2(8192.0 / wmax)), 0), 15) if wmax > 0 else 0
+
+
+def conv3(x, w, b, fmt, mode, S=None, **kw):
+    """One convolution in the emulated arithmetic.  mode: 'x3' three products, 'x1' single fp16 product.
+    S: the pair modes' per-conv weight scale 2^S (None: unscaled weights, the e4m3 rows with the former constants)."""
     xh, xl = pair(x)
-    wh, wl = pair(w)
+    wh, wl = pair(w if S is None or mode != 'x3' else w * 2.0 ** S)
+    whs, wls = (4, 15) if S is None else (-5, 6)
     y = F.conv2d(xh.double(), wh.double(), None, **kw)
     if mode == 'x3' and fmt == 'e4m3const':
         # hi parts as they are, lo parts times 2^11 (|lo| <= 2^-11 |hi|), every tensor with the same constants
-        y = y + F.conv2d(const_quant(xl, 11).double(), const_quant(wh, 4).double(), None, **kw) \
-              + F.conv2d(const_quant(xh, 0).double(), const_quant(wl, 15).double(), None, **kw)
+        y = y + F.conv2d(const_quant(xl, 11).double(), const_quant(wh, whs).double(), None, **kw) \
+              + F.conv2d(const_quant(xh, 0).double(), const_quant(wl, wls).double(), None, **kw)
     elif mode == 'x3':
         wq = lambda t: mx_quant(t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]), fmt).reshape(t.shape[0], t.shape[2], t.shape[3], t.shape[1]).permute(0, 3, 1, 2)
         aq = lambda t: mx_quant(t, fmt)
         y = y + F.conv2d(aq(xl).double(), wq(wh).double(), None, **kw) + F.conv2d(aq(xh).double(), wq(wl).double(), None, **kw)
+    if S is not None and mode == 'x3':
+        y = y * 2.0 ** -S
     return (y + b.double()[None, :, None, None]).float()
 
 
-def sim(x, sd, fmt, mode, stem_single=False):
+def sim(x, sd, fmt, mode, stem_single=False, wscale=True):
     sd = R.canonical_state_dict(sd)
     w, b = fold(sd, 'conv1', 'bn1')
     if stem_single:
@@ -89,20 +110,31 @@ def sim(x, sd, fmt, mode, stem_single=False):
             p = f'{name}.{blk}'
             st = stride if blk == 0 else 1
             w1, b1 = fold(sd, p + '.conv1', p + '.bn1'); w2, b2 = fold(sd, p + '.conv2', p + '.bn2')
-            t = F.relu(conv3(y, w1, b1, fmt, mode, stride=st, padding=1))
+            S1 = pair_shift(w1) if wscale else None
+            S2 = pair_shift(w2) if wscale else None
+            t = F.relu(conv3(y, w1, b1, fmt, mode, S1, stride=st, padding=1))
             if (p + '.downsample.0.weight') in sd:
                 wd, bd = fold(sd, p + '.downsample.0', p + '.downsample.1')
-                ident = conv3(y, wd, bd, fmt, mode, stride=st)
+                S2 = pair_shift(w2, wd) if wscale else None  # the projection rides in conv2's accumulator: one S
+                ident = conv3(y, wd, bd, fmt, mode, S2, stride=st)
             else:
                 ident = y
-            y = F.relu(conv3(t, w2, b2, fmt, mode, padding=1) + ident)
+            y = F.relu(conv3(t, w2, b2, fmt, mode, S2, padding=1) + ident)
     f = torch.flatten(F.adaptive_avg_pool2d(y, 1), 1)
     return f, F.linear(f, sd['fc.weight'], sd['fc.bias'])
 
 
 rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-sd = synth.seeded_resnet18_state_dict(0, num_classes=2)
+ap = argparse.ArgumentParser()
+ap.add_argument('n_patches', nargs='?', type=int, default=32)
+ap.add_argument('--rescale', type=int, default=0, metavar='K')
+ap.add_argument('--no-wscale', dest='wscale', action='store_false')
+ap.add_argument('--seed', type=int, default=0)
+args = ap.parse_args()
+N = args.n_patches
+sd = synth.seeded_resnet18_state_dict(args.seed, num_classes=2)
+if args.rescale:
+    sd = rescale_cases.rescale_inner(sd, args.rescale, seed=100 + args.seed)
 u8 = synth.synth_patches_u8(N, seed=1)
 lut = torch.from_numpy(T.normalize_lut())
 x = torch.stack([lut[c][u8[..., c].long()] for c in range(3)], dim=1)
@@ -111,8 +143,8 @@ with torch.no_grad():
     for nm, fmt, mode in [('cross terms e4m3, constant scales', 'e4m3const', 'x3'),
                           ('fp16x3 (exact cross terms)', None, 'x3'), ('cross terms MXFP8 e4m3', 'e4m3', 'x3'),
                           ('cross terms MXFP6 e2m3', 'e2m3', 'x3'), ('single fp16 product', None, 'x1')]:
-        f, l = sim(x, sd, fmt, mode)
+        f, l = sim(x, sd, fmt, mode, wscale=args.wscale)
         if fmt == 'e4m3const':
-            f1, l1 = sim(x, sd, fmt, mode, stem_single=True)
+            f1, l1 = sim(x, sd, fmt, mode, stem_single=True, wscale=args.wscale)
             print(f"{'... with a one-product stem':30s} feats {rel(f1, rf):.2e} logits {rel(l1, rl):.2e} labels equal {bool((l1.argmax(1) == rl.argmax(1)).all())}", flush=True)
         print(f'{nm:30s} feats {rel(f, rf):.2e} logits {rel(l, rl):.2e} labels equal {bool((l.argmax(1) == rl.argmax(1)).all())}', flush=True)
