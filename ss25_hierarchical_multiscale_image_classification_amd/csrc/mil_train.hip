@@ -48,11 +48,7 @@ static MilTrainPlan make_mil_train_plan(const hipac_mil_params_t* p, int pooling
   q.A_pad = att ? (p->attn_dim + 31) / 32 * 32 : 0;
   q.ntiles = (n + kMtTile - 1) / kMtTile;
   q.nseg = q.ntiles + n_bags;
-  // dV: one workgroup = 64 feature columns x all of A x one slice of rows; about 512 workgroups in all
-  const int fchunks = (p->feature_dim + 63) / 64;
-  const int target = 512 / fchunks > 0 ? 512 / fchunks : 1;
-  q.chunk = ((n + target - 1) / target + 31) / 32 * 32;
-  q.slices = (n + q.chunk - 1) / q.chunk;
+  mil_train_dv_slices(n, p->feature_dim, &q.chunk, &q.slices);
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
@@ -539,6 +535,48 @@ int mil_train_run(const hipac_mil_params_t* p, int pooling, const float* feats, 
     HIPAC_CHECK_HIP(hipGetLastError());
   }
   return 0;
+}
+
+// mil_train_internal.h: the launches of the kernels above that do not depend on the number of attention heads, for
+// mil_heads.hip.  The same launch shapes as in mil_train_run.
+bool mil_train_sizes_ok(const hipac_mil_params_t* p, int n, int n_bags) { return mil_train_dims_ok(p, HIPAC_MIL_ATTENTION, n, n_bags); }
+
+// dV: one workgroup = 64 feature columns x all of A x one slice of rows; about 512 workgroups in all
+void mil_train_dv_slices(int n, int F, int* chunk, int* slices) {
+  const int fchunks = (F + 63) / 64;
+  const int target = 512 / fchunks > 0 ? 512 / fchunks : 1;
+  *chunk = ((n + target - 1) / target + 31) / 32 * 32;
+  *slices = (n + *chunk - 1) / *chunk;
+}
+
+void mil_train_launch_bag_of(const int32_t* offs, int n_bags, int n, int32_t* bag_of, hipStream_t s) {
+  hipLaunchKernelGGL(mt_bag_of_kernel, dim3((n + 255) / 256), dim3(256), 0, s, offs, n_bags, n, bag_of);
+}
+
+void mil_train_launch_h(const float* feats, const int32_t* rows, int n, int F, const float* Vw, const float* Vb, int A, int A_pad,
+                        float* H, hipStream_t s) {
+  hipLaunchKernelGGL(mt_h_kernel, dim3((n + kMtTile - 1) / kMtTile, (A + 63) / 64), dim3(256), 0, s, feats, rows, n, F, Vw, Vb, A,
+                     A_pad, H);
+}
+
+void mil_train_launch_pool_combine(const float* part, const int32_t* offs, int n_bags, int F, float* pooled, hipStream_t s) {
+  hipLaunchKernelGGL(mt_pool_combine_kernel, dim3(n_bags, (F + 31) / 32), dim3(256), 0, s, part, offs, F, (int)HIPAC_MIL_ATTENTION,
+                     pooled);
+}
+
+void mil_train_launch_cdot(const float* pooled, const float* g, int F, int B, float* cdot, hipStream_t s) {
+  hipLaunchKernelGGL(mt_cdot_kernel, dim3((B + 3) / 4), dim3(256), 0, s, pooled, g, F, B, cdot);
+}
+
+void mil_train_launch_slab_reduce(const float* part, int slices, size_t per_slice, size_t off, long long count, float* dst,
+                                  int accumulate, hipStream_t s) {
+  hipLaunchKernelGGL(mt_slab_reduce_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, s, part, slices, per_slice, off, count,
+                     dst, accumulate);
+}
+
+void mil_train_launch_dv(const float* dH, const float* feats, const int32_t* rows, int n, int F, int A, int A_pad, int chunk,
+                         int slices, float* slab, hipStream_t s) {
+  hipLaunchKernelGGL(mt_dv_kernel, dim3((F + 63) / 64, slices), dim3(256), 0, s, dH, feats, rows, n, F, A, A_pad, chunk, slab);
 }
 
 }  // namespace hipac

@@ -48,6 +48,10 @@ evaluation masks made on the device (``froc.py``); it writes ``froc_results.json
 ``experiments/experiment_configs.yaml``) on the ``patch_features_L.npy`` / ``patch_labels_L.npy`` / ``patch_paths_L.txt``
 triple of ``--patch_level L`` in the working directory and writes ``models/mil_model.pth`` and ``results/metrics.json``;
 ``--predict_mil`` scores every bag of the triple with ``--mil_model`` into ``results/mil_predictions.csv``.
+``--mil_heads K`` (1..8, the yaml's ``attention_heads: 8``) trains multi-head attention pooling (``mil_heads.py``): K
+softmaxes over one shared hidden layer, the K pooled vectors concatenated; ``--predict_mil`` reads K from the saved model.
+``--mil_save_attention`` makes ``--predict_mil`` also write ``results/mil_attention.npy``, float32 [patches, K] in the
+order of ``patch_paths_L.txt``.
 
 Everything else outside the hot path (download, plots) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
@@ -136,6 +140,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mil_mc_samples", type=int, default=0, metavar="T",
                    help="--predict_mil: also run T Monte-Carlo dropout forwards per bag -> results/mil_uncertainty.csv "
                         "(the reference's yaml: 100; needs --mil_dropout > 0)")
+    p.add_argument("--mil_heads", type=int, default=None, metavar="K",
+                   help="attention heads of the MIL head, 1..8 (the reference's yaml: 8; default 1): K softmaxes over one shared "
+                        "hidden layer, the K pooled vectors concatenated in front of the classifier.  Attention pooling only, and "
+                        "not with --mil_dropout / --mil_mc_samples.  --predict_mil reads K from the model; if given it must agree")
+    p.add_argument("--mil_save_attention", action="store_true",
+                   help="--predict_mil with attention pooling: also write results/mil_attention.npy, float32 [patches, K], row i "
+                        "= the attention weights of line i of patch_paths_L.txt inside its bag")
     p.add_argument("--mil_threshold", type=float, default=0.5, help="--mil_mc_samples: prediction = mean probability > this")
     p.add_argument("--detect", action="store_true",
                    help="write the detection CSVs --run_evaluation scores: dense scan of <data_root>/test/img at the levels of "
@@ -493,6 +504,21 @@ def mil_triple(args):
     return triple
 
 
+def check_mil_args(parser, args):
+    """The combinations of the MIL flags that are refused, as argparse errors (exit status 2), before anything else runs."""
+    heads = args.mil_heads
+    if heads is not None and not 1 <= heads <= 8:
+        parser.error(f"--mil_heads {heads}: give 1 .. 8 attention heads")
+    if heads is not None and heads > 1:
+        if args.mil_pooling != "attention":
+            parser.error(f"--mil_heads {heads} needs --mil_pooling attention: {args.mil_pooling} pooling has no attention to branch")
+        if args.mil_dropout > 0.0 or args.mil_mc_samples > 0:
+            parser.error(f"--mil_heads {heads} with --mil_dropout / --mil_mc_samples is not implemented: the dropout step and the "
+                         "Monte-Carlo pass are single-head")
+    if args.mil_save_attention and args.mil_pooling != "attention":
+        parser.error(f"--mil_save_attention needs --mil_pooling attention: {args.mil_pooling} pooling has no attention weights")
+
+
 def cmd_mil(args, train: bool):
     triple = mil_triple(args)  # before anything touches a GPU
     if triple is None:
@@ -516,13 +542,19 @@ def cmd_mil(args, train: bool):
     if train:
         mil_train.train_mil(*triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, epochs=args.mil_epochs,
                             bags_per_step=args.mil_bags_per_step, bag_size=args.mil_bag_size,
-                            seed=0 if args.seed is None else args.seed, max_steps=args.max_steps, dropout=args.mil_dropout)
+                            seed=0 if args.seed is None else args.seed, max_steps=args.max_steps, dropout=args.mil_dropout,
+                            heads=1 if args.mil_heads is None else args.mil_heads)
         return 0
     if not os.path.exists(args.mil_model):
         print(f"[ERROR] {args.mil_model} not found: run --train_mil first or give --mil_model PATH.")
         return 2
-    mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, dropout=args.mil_dropout,
-                          mc_samples=args.mil_mc_samples, threshold=args.mil_threshold, seed=0 if args.seed is None else args.seed)
+    try:
+        mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, dropout=args.mil_dropout,
+                              mc_samples=args.mil_mc_samples, threshold=args.mil_threshold, seed=0 if args.seed is None else args.seed,
+                              heads=args.mil_heads, save_attention=args.mil_save_attention)
+    except ValueError as e:  # the model's head count against the flags
+        print(f"[ERROR] --predict_mil: {e}")
+        return 2
     return 0
 
 
@@ -536,7 +568,9 @@ def _seed_everything(seed: int):
 
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_mil_args(parser, args)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")

@@ -7,6 +7,9 @@
   no CPU fallback; in ``train()`` mode it runs the ordinary autograd graph, under the dropout masks of
   ``mil_dropout.host_mask`` when ``dropout > 0`` (applied functionally: no module, no new state_dict key).
   ``forward_bags`` scores MANY bags in one launch pair (the reference loops over bags).
+  ``heads=K`` (1..8, the yaml's ``attention_heads``) is multi-head attention pooling: ``attn_U`` is ``Linear(attn_dim, K)``,
+  one softmax per head, the K pooled vectors concatenated in front of ``classifier.0`` = ``Linear(K * feature_dim, hidden)``;
+  same keys, and ``eval()`` runs ``hipac_mil_heads_forward`` (``mil_heads.py``) when K > 1.  K = 1 is the reference's model.
 * ``group_patches_by_wsi`` / ``WSIMILDDataset`` -- src/datasets/mildataset.py:6-47.  By default the
   bag key is the reference's as written: ``'_'.join(basename.split('_')[:-2])``, which for the patch
   names ``{slide}_x{x}_y{y}_{label}.png`` keeps the ``_x{x}`` field (one bag per slide COLUMN);
@@ -67,34 +70,50 @@ class WSIMILDDataset(torch.utils.data.Dataset):
 
 
 class MILAttentionPooling(nn.Module):
-    """mil_classifier.py:5-18 (ABMIL, Ilse et al.)."""
+    """mil_classifier.py:5-18 (ABMIL, Ilse et al.).  ``heads`` = K attention branches over the shared hidden layer
+    (the yaml's ``attention_heads``): ``attn_U`` is ``Linear(attn_dim, K)``, the softmax runs per head over the bag, and
+    ``forward`` returns the K pooled vectors concatenated head-major (K * in_dim) and the attention (N, K).  K = 1 is
+    the reference's module."""
 
-    def __init__(self, in_dim, attn_dim=128):
+    def __init__(self, in_dim, attn_dim=128, heads=1):
         super().__init__()
+        from .mil_heads import check_heads
+
+        self.heads = check_heads(heads)
         self.attn_V = nn.Linear(in_dim, attn_dim)
-        self.attn_U = nn.Linear(attn_dim, 1)
+        self.attn_U = nn.Linear(attn_dim, self.heads)
 
     def forward(self, x):
         a = torch.softmax(self.attn_U(torch.tanh(self.attn_V(x))), dim=0)
-        return torch.sum(a * x, dim=0), a
+        # M[k] = sum_i a[i][k] x[i]; for one head this is the reference's torch.sum(a * x, dim=0), bit for bit
+        pooled = torch.stack([torch.sum(a[:, k:k + 1] * x, dim=0) for k in range(self.heads)])
+        return pooled.reshape(-1), a
 
 
 class MILClassifier(nn.Module):
-    """mil_classifier.py:20-45."""
+    """mil_classifier.py:20-45.  ``heads`` > 1 (attention pooling only): multi-head attention pooling, ``classifier.0``
+    takes ``heads * feature_dim`` columns; the state_dict keys are the same.  ``attn_dim`` / ``hidden_dim`` are the
+    reference's 128 unless given."""
 
-    def __init__(self, feature_dim, num_classes=2, pooling="attention", dropout=0.0, dropout_seed=0):
+    def __init__(self, feature_dim, num_classes=2, pooling="attention", dropout=0.0, dropout_seed=0, heads=1, attn_dim=128,
+                 hidden_dim=128):
         super().__init__()
+        from .mil_heads import check_heads
+
         if pooling not in ("attention", "mean", "max"):
             raise ValueError("Unknown pooling: choose from 'attention', 'mean', 'max'")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError("dropout must satisfy 0 <= p < 1")
+        self.heads = check_heads(heads)
+        if self.heads != 1 and pooling != "attention":
+            raise ValueError(f"heads = {self.heads} needs attention pooling: {pooling} pooling has no attention to branch")
         self.pooling = pooling
         # plain attributes, not parameters or buffers: the state_dict keeps the reference's keys.  dropout_step is the
         # mask's sample index (the trainer's step number); the caller advances it.
         self.dropout, self.dropout_seed, self.dropout_step = float(dropout), int(dropout_seed), 0
         if pooling == "attention":
-            self.aggregator = MILAttentionPooling(feature_dim)
-        self.classifier = nn.Sequential(nn.Linear(feature_dim, 128), nn.ReLU(), nn.Linear(128, num_classes))
+            self.aggregator = MILAttentionPooling(feature_dim, attn_dim, self.heads)
+        self.classifier = nn.Sequential(nn.Linear(self.heads * feature_dim, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, num_classes))
 
     def _aggregate(self, bag):
         if self.pooling == "attention":
@@ -103,14 +122,20 @@ class MILClassifier(nn.Module):
 
     def forward_bags(self, feats: torch.Tensor, bag_offsets, want_pooled: bool = False):
         """HIP path for many bags: feats float32[n,F] (bag rows contiguous, on a ROCm device),
-        bag_offsets int[n_bags+1] -> (logits[n_bags,C], attn[n] or None[, pooled[n_bags,F]])."""
+        bag_offsets int[n_bags+1] -> (logits[n_bags,C], attn[n] or None[, pooled[n_bags,F]]).  A model of K > 1 heads
+        (the rows of ``aggregator.attn_U.weight``) runs ``hipac_mil_heads_forward``: attn[n,K], pooled[n_bags,K F]."""
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         offs = torch.as_tensor(np.asarray(bag_offsets)) if not torch.is_tensor(bag_offsets) else bag_offsets
-        logits, attn, pooled = capi.mil_forward(sd, self.pooling, feats.contiguous(), offs, want_pooled=want_pooled)
+        if self.pooling == "attention" and int(sd["aggregator.attn_U.weight"].shape[0]) != 1:
+            from .mil_heads import heads_forward
+
+            logits, attn, pooled = heads_forward(sd, feats.contiguous(), offs, want_pooled=want_pooled)
+        else:
+            logits, attn, pooled = capi.mil_forward(sd, self.pooling, feats.contiguous(), offs, want_pooled=want_pooled)
         return (logits, attn, pooled) if want_pooled else (logits, attn)
 
     def forward(self, bag, row0=0, bag_index=0):
-        """bag: (num_patches, feature_dim) -> (logits (num_classes), attention (num_patches, 1) or None).  ``row0`` (the
+        """bag: (num_patches, feature_dim) -> (logits (num_classes), attention (num_patches, heads) or None).  ``row0`` (the
         position of the bag's first row in the batch) and ``bag_index`` place the bag in the dropout masks; they matter in
         ``train()`` mode with ``dropout > 0`` only."""
         if self.training:
@@ -124,7 +149,7 @@ class MILClassifier(nn.Module):
             pooled, attn = self._aggregate(bag)
             return self.classifier(pooled), attn
         logits, attn = self.forward_bags(bag, torch.tensor([0, bag.shape[0]]))
-        return logits[0], (None if attn is None else attn.unsqueeze(1))
+        return logits[0], (None if attn is None else attn.reshape(bag.shape[0], -1))
 
     def predict(self, bag):
         """Class probabilities of one bag (the reference's ``predict`` does not run as written: it applies a

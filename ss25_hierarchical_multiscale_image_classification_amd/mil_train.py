@@ -10,6 +10,9 @@ decay 1e-4, 50 epochs, 32 bags per step, early stopping with patience 5, a 0.8 /
   rows of the resident feature matrix, the L2 term, ``hipac_adam_step``.
 * ``train_mil`` / ``predict_mil``: the loop and the scoring over the (features, labels, paths) triple that
   ``--extract_features`` writes.  Validation and prediction go through ``MILClassifier.forward_bags``.
+* Multi-head attention pooling (the yaml's ``attention_heads``, ``--mil_heads K``) comes from ``mil_heads.py``: a model
+  whose ``aggregator.attn_U.weight`` has K > 1 rows trains through ``hipac_mil_heads_train_fwd_bwd`` and is scored through
+  ``hipac_mil_heads_forward``; one head goes the way it always went.
 * Dropout (the yaml's ``dropout_rate``) and Monte-Carlo dropout uncertainty (its ``uncertainty_estimation``) come from
   ``mil_dropout.py``: the trainer's step under ``hipac_mil_dropout_train_fwd_bwd``, ``predict_mil``'s
   ``results/mil_uncertainty.csv`` from ``mil_dropout.mc_forward``.
@@ -24,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import capi, mil_dropout
+from . import capi, mil_dropout, mil_heads
 from .mil import MILClassifier, group_patches_by_wsi
 from .train_native import FlatAdam
 
@@ -64,23 +67,30 @@ class NativeMILTrainer:
     """``MILClassifier`` under torch.optim.Adam(lr, weight_decay) with the whole step in HIP.  ``sd``: a MILClassifier
     state_dict (any device, converted to float32); the parameters live in one flat buffer, every tensor starting on a
     16-byte boundary (the gaps stay 0).  ``dropout`` > 0: every forward_backward runs under the masks of
-    (``seed``, sample = the number of steps taken so far) -- include/hipac_mil_dropout.h; 0 is the step as it always was."""
+    (``seed``, sample = the number of steps taken so far) -- include/hipac_mil_dropout.h; 0 is the step as it always was.
+    The head count is the number of rows of ``aggregator.attn_U.weight``: more than one runs
+    ``hipac_mil_heads_train_fwd_bwd`` (include/hipac_mil_heads.h; not under dropout), one ``hipac_mil_train_fwd_bwd``."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], pooling: str, device, lr: float = 1e-3, weight_decay: float = 1e-4,
                  class_weights=None, dropout: float = 0.0, seed: int = 0):
         if pooling not in capi.MIL_POOLING:
             raise ValueError("Unknown pooling: choose from 'attention', 'mean', 'max'")
-        self.lib = load_mil_train_library()
-        self.dropout, self.seed, self.steps = mil_dropout.check_p(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF, 0
-        if self.dropout > 0.0:
-            mil_dropout.load_mil_dropout_library()
-        self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
-        if self.device.type != "cuda":
-            raise capi.HipacError("NativeMILTrainer needs a ROCm device: there is no CPU fallback")
         self.keys = [k for k, _ in PARAM_FIELDS if pooling == "attention" or not k.startswith("aggregator.")]
         missing = [k for k in self.keys if k not in sd]
         if missing:
             raise capi.HipacError(f"state_dict lacks {missing}")
+        self.heads = mil_heads.model_dims(sd, pooling)[0]  # ValueError if classifier.0.weight disagrees with heads * feature_dim
+        self.dropout, self.seed, self.steps = mil_dropout.check_p(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        if self.heads > 1 and self.dropout > 0.0:
+            raise ValueError("dropout with more than one attention head is not implemented: the masked step is single-head")
+        self.lib = load_mil_train_library()
+        if self.dropout > 0.0:
+            mil_dropout.load_mil_dropout_library()
+        if self.heads > 1:
+            mil_heads.load_mil_heads_library()
+        self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
+        if self.device.type != "cuda":
+            raise capi.HipacError("NativeMILTrainer needs a ROCm device: there is no CPU fallback")
         self.shapes = {k: tuple(sd[k].shape) for k in self.keys}
         self.offsets, o = {}, 0
         for k in self.keys:
@@ -89,11 +99,14 @@ class NativeMILTrainer:
         self.opt = FlatAdam(o, self.device, lr)
         for k in self.keys:
             self._view(self.opt.params, k).copy_(sd[k].detach().to(self.device, torch.float32))
-        self.F, self.hidden = int(self.shapes["classifier.0.weight"][1]), int(self.shapes["classifier.0.weight"][0])
+        self.F, self.hidden = int(self.shapes["classifier.0.weight"][1]) // self.heads, int(self.shapes["classifier.0.weight"][0])
         self.C = int(self.shapes["classifier.2.weight"][0])
         self.A = int(self.shapes["aggregator.attn_V.weight"][0]) if pooling == "attention" else 0
         if pooling == "attention" and self.shapes["aggregator.attn_V.weight"] != (self.A, self.F):
             raise capi.HipacError("aggregator.attn_V.weight does not match feature_dim")
+        if pooling == "attention" and (self.shapes["aggregator.attn_U.weight"] != (self.heads, self.A) or
+                                       self.shapes["aggregator.attn_U.bias"] != (self.heads,)):
+            raise capi.HipacError("aggregator.attn_U does not match aggregator.attn_V")
         if self.shapes["classifier.2.weight"] != (self.C, self.hidden):
             raise capi.HipacError("classifier.2.weight does not match classifier.0.weight")
         self._p, self._g = self._struct(self.opt.params), self._struct(self.opt.grads)
@@ -127,7 +140,8 @@ class NativeMILTrainer:
                          ) -> Tuple[torch.Tensor, torch.Tensor]:
         """feats float32[N, F] on the device (stays in place); rows int[n] indices into it, or None for
         the identity (then offsets must end at N); offsets int[n_bags + 1]; labels int64[n_bags] -> (loss float32[], logits[n_bags, C]);
-        the gradients land in the flat buffer (``grad_dict``).  Everything is checked on the host before the launch: a
+        the gradients land in the flat buffer (``grad_dict``); ``want_attn`` keeps the softmax weights in ``self.attn``
+        ([n], or [n, heads] for more than one head).  Everything is checked on the host before the launch: a
         bad row index never reaches a kernel."""
         if not torch.is_tensor(feats) or not feats.is_cuda:
             raise capi.HipacError("HIP path called with a CPU tensor: there is no CPU fallback (move inputs to cuda)")
@@ -163,7 +177,10 @@ class NativeMILTrainer:
         lab = lab.to(self.device).contiguous()
         offs_dev = torch.from_numpy(offs.astype(np.int32)).to(self.device)
         pool = capi.MIL_POOLING[self.pooling]
-        query = self.lib.hipac_mil_dropout_train_workspace_bytes if self.dropout > 0.0 else self.lib.hipac_mil_train_workspace_bytes
+        if self.heads > 1:  # `heads` takes the place of `pooling` in both calls
+            pool, query = self.heads, self.lib.hipac_mil_heads_train_workspace_bytes
+        else:
+            query = self.lib.hipac_mil_dropout_train_workspace_bytes if self.dropout > 0.0 else self.lib.hipac_mil_train_workspace_bytes
         need = query(C.addressof(self._p), pool, n, n_bags)
         if need == 0:
             raise capi.HipacError(f"mil training step of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
@@ -171,16 +188,20 @@ class NativeMILTrainer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         logits = torch.empty((n_bags, self.C), dtype=torch.float32, device=self.device)
-        self.attn = torch.empty(n, dtype=torch.float32, device=self.device) if (want_attn and self.pooling == "attention") else None
+        self.attn = torch.empty(n if self.heads == 1 else (n, self.heads), dtype=torch.float32, device=self.device) \
+            if (want_attn and self.pooling == "attention") else None
         args = (C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
                 lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
                 capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0)
         with torch.cuda.device(self.device):
-            if self.dropout > 0.0:
+            if self.heads > 1:
+                rc = self.lib.hipac_mil_heads_train_fwd_bwd(*args, capi._stream())
+            elif self.dropout > 0.0:
                 rc = self.lib.hipac_mil_dropout_train_fwd_bwd(*args, self.dropout, self.seed, self.steps & 0xFFFFFFFF, capi._stream())
             else:
                 rc = self.lib.hipac_mil_train_fwd_bwd(*args, capi._stream())
-        capi._check(rc, "hipac_mil_dropout_train_fwd_bwd" if self.dropout > 0.0 else "hipac_mil_train_fwd_bwd")
+        capi._check(rc, "hipac_mil_heads_train_fwd_bwd" if self.heads > 1 else
+                    "hipac_mil_dropout_train_fwd_bwd" if self.dropout > 0.0 else "hipac_mil_train_fwd_bwd")
         return loss, logits
 
     def step(self, feats, rows, offsets, labels) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -255,12 +276,12 @@ def load_triple(features_path, labels_path, paths_path, by_slide: bool = False):
     return np.ascontiguousarray(feats, dtype=np.float32), order, offsets, names, wsi
 
 
-def initial_state_dict(feature_dim: int, pooling: str, seed: int) -> Dict[str, torch.Tensor]:
+def initial_state_dict(feature_dim: int, pooling: str, seed: int, heads: int = 1) -> Dict[str, torch.Tensor]:
     """MILClassifier's own (torch default) initialisation under ``torch.manual_seed(seed)``, drawn on the CPU."""
     gen_state = torch.get_rng_state()
     torch.manual_seed(seed)
     try:
-        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling).state_dict().items()}
+        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling, heads=heads).state_dict().items()}
     finally:
         torch.set_rng_state(gen_state)
 
@@ -272,22 +293,33 @@ def _gathered(feats_dev: torch.Tensor, bags, order, offsets):
     return feats_dev[torch.from_numpy(rows).to(feats_dev.device)].contiguous(), offs
 
 
-def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray) -> torch.Tensor:
-    model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling).to(feats.device)
+def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray, want_attn: bool = False):
+    """The logits of the bags under the model ``sd`` (its head count read from the state_dict); with ``want_attn`` also the
+    attention [n, heads] (None for mean / max pooling)."""
+    heads = mil_heads.model_dims(sd, pooling)[0]
+    model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling, heads=heads).to(feats.device)
     model.load_state_dict(sd, strict=True)
     model.eval()
-    return model.forward_bags(feats, offs)[0]
+    logits, attn = model.forward_bags(feats, offs)
+    if not want_attn:
+        return logits
+    return logits, (None if attn is None else attn.reshape(feats.shape[0], heads))
 
 
 def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False, epochs: int = 50,
               bags_per_step: int = 32, bag_size: Optional[int] = None, lr: float = 1e-3, weight_decay: float = 1e-4,
               patience: int = 5, seed: int = 0, out_dir: str = ".", max_steps: Optional[int] = None, device=None,
-              dropout: float = 0.0) -> Dict[str, object]:
+              dropout: float = 0.0, heads: int = 1) -> Dict[str, object]:
     """The yaml's loop (module docstring).  Writes ``<out_dir>/models/mil_model.pth`` (the state with the best validation
     loss; the last one when there is no validation split) and ``<out_dir>/results/metrics.json``; returns the metrics.
     ``dropout`` > 0 trains under dropout (masks seeded by ``seed``); validation and test scoring stay deterministic, and
-    the metrics then carry a ``"dropout"`` key."""
-    dropout = mil_dropout.check_p(dropout)
+    the metrics then carry a ``"dropout"`` key.  ``heads`` > 1 (attention pooling, no dropout) trains the multi-head model
+    and the metrics carry ``"attention_heads"``."""
+    dropout, heads = mil_dropout.check_p(dropout), mil_heads.check_heads(heads)
+    if heads > 1 and pooling != "attention":
+        raise ValueError(f"heads = {heads} needs attention pooling, not {pooling}")
+    if heads > 1 and dropout > 0.0:
+        raise ValueError("dropout with more than one attention head is not implemented: the masked step is single-head")
     feats, order, offsets, names, wsi = load_triple(features_path, labels_path, paths_path, by_slide)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     tr, va, te = split_bags(len(names), seed)
@@ -295,7 +327,7 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
     if len(va) == 0:
         print("[INFO] MIL: the validation split is empty: early stopping is off")
     feats_dev = torch.from_numpy(feats).to(dev)  # uploaded once; every step reads it in place through a row index
-    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed), pooling, dev, lr=lr, weight_decay=weight_decay,
+    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed, heads), pooling, dev, lr=lr, weight_decay=weight_decay,
                                dropout=dropout, seed=seed)
     labels_all = torch.from_numpy(wsi)
     val = _gathered(feats_dev, va, order, offsets) if len(va) else None
@@ -345,6 +377,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
                     "split_sizes": {"train": int(len(tr)), "val": int(len(va)), "test": int(len(te))}})
     if dropout > 0.0:
         metrics["dropout"] = dropout
+    if heads > 1:
+        metrics["attention_heads"] = heads
     with open(os.path.join(out_dir, "results", "metrics.json"), "w") as f:
         json.dump(metrics, f, indent=2)
     print(f"[INFO] MIL: model saved to {model_path}; test accuracy {metrics['accuracy']:.4f}")
@@ -352,13 +386,16 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
 
 
 def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False,
-                out_dir: str = ".", device=None, dropout: float = 0.0, mc_samples: int = 0, threshold: float = 0.5, seed: int = 0
-                ) -> List[Tuple[str, float, int]]:
+                out_dir: str = ".", device=None, dropout: float = 0.0, mc_samples: int = 0, threshold: float = 0.5, seed: int = 0,
+                heads: Optional[int] = None, save_attention: bool = False) -> List[Tuple[str, float, int]]:
     """Every bag of the triple scored with a saved model -> [(bag name, probability of class 1, predicted label)], also
     written as ``<out_dir>/results/mil_predictions.csv``.  With ``mc_samples`` > 0 (needs ``dropout`` > 0) it also writes
     ``<out_dir>/results/mil_uncertainty.csv``: per bag the mean and the variance (divisor T - 1, ``torch.var``) of the
     class-1 probability over ``mc_samples`` stochastic forwards, the entropy of the mean, the mean entropy, their difference
-    (the mutual information), and ``mean_probability > threshold`` (the reference's ``softmax_thresholding``)."""
+    (the mutual information), and ``mean_probability > threshold`` (the reference's ``softmax_thresholding``).
+    The head count is the saved model's; ``heads``, when given, must agree with it.  ``save_attention`` (attention pooling)
+    also writes ``<out_dir>/results/mil_attention.npy``: float32 [n, heads], row i the softmax weights of the patch on line
+    i of the paths file inside its bag -- what the reference's src/visualization/attention_heatmap.py takes."""
     dropout, mc_samples = mil_dropout.check_p(dropout), int(mc_samples)
     if mc_samples < 0 or mc_samples > mil_dropout.MC_MAX_SAMPLES:
         raise ValueError(f"mc_samples must be in 0..{mil_dropout.MC_MAX_SAMPLES}, got {mc_samples}")
@@ -368,9 +405,16 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
     feats, order, offsets, names, _ = load_triple(features_path, labels_path, paths_path, by_slide)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     sd = {k: v.to(dev, torch.float32).contiguous() for k, v in torch.load(model_path, map_location="cpu", weights_only=True).items()}
+    model_heads = mil_heads.model_dims(sd, pooling)[0]
+    if heads is not None and mil_heads.check_heads(heads) != model_heads:
+        raise ValueError(f"heads = {heads}, but {model_path} has {model_heads} attention head(s)")
+    if model_heads > 1 and (dropout > 0.0 or mc_samples > 0):
+        raise ValueError("Monte-Carlo dropout with more than one attention head is not implemented: the fused pass is single-head")
+    if save_attention and pooling != "attention":
+        raise ValueError(f"save_attention needs attention pooling: {pooling} pooling has no attention weights")
     feats_dev = torch.from_numpy(feats).to(dev)
     f, offs = _gathered(feats_dev, np.arange(len(names)), order, offsets)
-    logits = _score(sd, pooling, f, offs)
+    logits, attn = _score(sd, pooling, f, offs, want_attn=True)
     prob = torch.softmax(logits, dim=1)[:, 1].cpu().numpy()
     pred = logits.argmax(1).cpu().numpy()
     out = [(n, float(p), int(y)) for n, p, y in zip(names, prob, pred)]
@@ -380,6 +424,12 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
         for n, p, y in out:
             fh.write(f"{n},{p:.6f},{y}\n")
     print(f"[INFO] MIL: {len(out)} bags scored -> {os.path.join(out_dir, 'results', 'mil_predictions.csv')}")
+    if save_attention:
+        table = np.empty((feats.shape[0], model_heads), np.float32)
+        table[order] = attn.cpu().numpy()  # gathered row i is line order[i] of the paths file
+        path = os.path.join(out_dir, "results", "mil_attention.npy")
+        np.save(path, table)
+        print(f"[INFO] MIL: attention of {model_heads} head(s) over {feats.shape[0]} patches -> {path}")
     if mc_samples > 0:
         if int(sd["classifier.2.weight"].shape[0]) < 2:
             raise ValueError("the uncertainty table reports class 1: the model needs at least two classes")
