@@ -296,6 +296,13 @@ static void mil_heads_pool(const hipac_mil_params_t* p, int K, const float* feat
   mil_train_launch_pool_combine(part, bag_offsets, n_bags, K * F, pooled, s);
 }
 
+void mil_heads_launch_pool(const float* feats, const int32_t* rows, const int32_t* bag_of, const float* a, int n, int F, int K,
+                           int ntiles, float* part, hipStream_t s) {
+#define MH_POOL(KK) hipLaunchKernelGGL(mh_pool_kernel<KK>, dim3(ntiles), dim3(256), 0, s, feats, rows, bag_of, a, n, F, part)
+  MH_FOR_HEADS(K, MH_POOL)
+#undef MH_POOL
+}
+
 }  // namespace hipac
 
 using namespace hipac;

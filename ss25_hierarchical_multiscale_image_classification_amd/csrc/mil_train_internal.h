@@ -34,5 +34,9 @@ void mil_train_launch_slab_reduce(const float* part, int slices, size_t per_slic
 // slab[slice][A][F] = dH^T X over the slice's rows
 void mil_train_launch_dv(const float* dH, const float* feats, const int32_t* rows, int n, int F, int A, int A_pad, int chunk,
                          int slices, float* slab, hipStream_t s);
+// mil_heads.hip's pooling partials for mil_gated.hip: tile t of 64 rows -> part[t + b][K][F] for every bag b it holds, from the
+// attention a [n][K]; K in 1..8, ntiles = ceil(n / 64)
+void mil_heads_launch_pool(const float* feats, const int32_t* rows, const int32_t* bag_of, const float* a, int n, int F, int K,
+                           int ntiles, float* part, hipStream_t s);
 
 }  // namespace hipac

@@ -52,6 +52,8 @@ triple of ``--patch_level L`` in the working directory and writes ``models/mil_m
 softmaxes over one shared hidden layer, the K pooled vectors concatenated; ``--predict_mil`` reads K from the saved model.
 ``--mil_save_attention`` makes ``--predict_mil`` also write ``results/mil_attention.npy``, float32 [patches, K] in the
 order of ``patch_paths_L.txt``.
+``--mil_gated`` trains the gated attention of Ilse et al. 2018 (``mil_gated.py``): a learned sigmoid gate ``aggregator.attn_G``
+over the hidden units, for any ``--mil_heads``; ``--predict_mil`` reads gatedness from the saved model and takes no flag.
 
 Everything else outside the hot path (download, plots) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
@@ -144,6 +146,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="attention heads of the MIL head, 1..8 (the reference's yaml: 8; default 1): K softmaxes over one shared "
                         "hidden layer, the K pooled vectors concatenated in front of the classifier.  Attention pooling only, and "
                         "not with --mil_dropout / --mil_mc_samples.  --predict_mil reads K from the model; if given it must agree")
+    p.add_argument("--mil_gated", action="store_true",
+                   help="--train_mil: gated attention (Ilse et al. 2018, eq. 9; CLAM's form): the score of a patch is "
+                        "U (tanh(V x) * sigmoid(G x)), with two more state_dict keys aggregator.attn_G.*.  Attention pooling only, "
+                        "any --mil_heads, not with --mil_dropout / --mil_mc_samples.  --predict_mil reads it from the model")
     p.add_argument("--mil_save_attention", action="store_true",
                    help="--predict_mil with attention pooling: also write results/mil_attention.npy, float32 [patches, K], row i "
                         "= the attention weights of line i of patch_paths_L.txt inside its bag")
@@ -515,6 +521,12 @@ def check_mil_args(parser, args):
         if args.mil_dropout > 0.0 or args.mil_mc_samples > 0:
             parser.error(f"--mil_heads {heads} with --mil_dropout / --mil_mc_samples is not implemented: the dropout step and the "
                          "Monte-Carlo pass are single-head")
+    if args.mil_gated:
+        if args.mil_pooling != "attention":
+            parser.error(f"--mil_gated needs --mil_pooling attention: {args.mil_pooling} pooling has no attention to gate")
+        if args.mil_dropout > 0.0 or args.mil_mc_samples > 0:
+            parser.error("--mil_gated with --mil_dropout / --mil_mc_samples is not implemented: the dropout step and the "
+                         "Monte-Carlo pass are single-head and ungated")
     if args.mil_save_attention and args.mil_pooling != "attention":
         parser.error(f"--mil_save_attention needs --mil_pooling attention: {args.mil_pooling} pooling has no attention weights")
 
@@ -543,7 +555,7 @@ def cmd_mil(args, train: bool):
         mil_train.train_mil(*triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, epochs=args.mil_epochs,
                             bags_per_step=args.mil_bags_per_step, bag_size=args.mil_bag_size,
                             seed=0 if args.seed is None else args.seed, max_steps=args.max_steps, dropout=args.mil_dropout,
-                            heads=1 if args.mil_heads is None else args.mil_heads)
+                            heads=1 if args.mil_heads is None else args.mil_heads, gated=args.mil_gated)
         return 0
     if not os.path.exists(args.mil_model):
         print(f"[ERROR] {args.mil_model} not found: run --train_mil first or give --mil_model PATH.")
@@ -552,7 +564,7 @@ def cmd_mil(args, train: bool):
         mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, dropout=args.mil_dropout,
                               mc_samples=args.mil_mc_samples, threshold=args.mil_threshold, seed=0 if args.seed is None else args.seed,
                               heads=args.mil_heads, save_attention=args.mil_save_attention)
-    except ValueError as e:  # the model's head count against the flags
+    except ValueError as e:  # the model's head count or its gate against the flags
         print(f"[ERROR] --predict_mil: {e}")
         return 2
     return 0

@@ -10,6 +10,10 @@
   ``heads=K`` (1..8, the yaml's ``attention_heads``) is multi-head attention pooling: ``attn_U`` is ``Linear(attn_dim, K)``,
   one softmax per head, the K pooled vectors concatenated in front of ``classifier.0`` = ``Linear(K * feature_dim, hidden)``;
   same keys, and ``eval()`` runs ``hipac_mil_heads_forward`` (``mil_heads.py``) when K > 1.  K = 1 is the reference's model.
+  ``gated=True`` is the gated attention of Ilse et al. 2018 (eq. 9, the form CLAM uses): the aggregator gains
+  ``attn_G = Linear(in_dim, attn_dim)`` (keys ``aggregator.attn_G.weight`` / ``.bias``, constructed last, so an ungated model
+  draws the same numbers and has the same keys as before) and scores a patch with ``attn_U(tanh(attn_V(x)) * sigmoid(attn_G(x)))``;
+  ``eval()`` runs ``hipac_mil_gated_forward`` (``mil_gated.py``) for any K.  A saved model is gated if it has the keys.
 * ``group_patches_by_wsi`` / ``WSIMILDDataset`` -- src/datasets/mildataset.py:6-47.  By default the
   bag key is the reference's as written: ``'_'.join(basename.split('_')[:-2])``, which for the patch
   names ``{slide}_x{x}_y{y}_{label}.png`` keeps the ``_x{x}`` field (one bag per slide COLUMN);
@@ -73,18 +77,24 @@ class MILAttentionPooling(nn.Module):
     """mil_classifier.py:5-18 (ABMIL, Ilse et al.).  ``heads`` = K attention branches over the shared hidden layer
     (the yaml's ``attention_heads``): ``attn_U`` is ``Linear(attn_dim, K)``, the softmax runs per head over the bag, and
     ``forward`` returns the K pooled vectors concatenated head-major (K * in_dim) and the attention (N, K).  K = 1 is
-    the reference's module."""
+    the reference's module.  ``gated``: the score is ``attn_U(tanh(attn_V(x)) * sigmoid(attn_G(x)))`` (Ilse et al. eq. 9);
+    ``attn_G`` is constructed after the other two, and only then."""
 
-    def __init__(self, in_dim, attn_dim=128, heads=1):
+    def __init__(self, in_dim, attn_dim=128, heads=1, gated=False):
         super().__init__()
         from .mil_heads import check_heads
 
-        self.heads = check_heads(heads)
+        self.heads, self.gated = check_heads(heads), bool(gated)
         self.attn_V = nn.Linear(in_dim, attn_dim)
         self.attn_U = nn.Linear(attn_dim, self.heads)
+        if self.gated:
+            self.attn_G = nn.Linear(in_dim, attn_dim)
 
     def forward(self, x):
-        a = torch.softmax(self.attn_U(torch.tanh(self.attn_V(x))), dim=0)
+        if self.gated:
+            a = torch.softmax(self.attn_U(torch.tanh(self.attn_V(x)) * torch.sigmoid(self.attn_G(x))), dim=0)
+        else:
+            a = torch.softmax(self.attn_U(torch.tanh(self.attn_V(x))), dim=0)
         # M[k] = sum_i a[i][k] x[i]; for one head this is the reference's torch.sum(a * x, dim=0), bit for bit
         pooled = torch.stack([torch.sum(a[:, k:k + 1] * x, dim=0) for k in range(self.heads)])
         return pooled.reshape(-1), a
@@ -93,10 +103,11 @@ class MILAttentionPooling(nn.Module):
 class MILClassifier(nn.Module):
     """mil_classifier.py:20-45.  ``heads`` > 1 (attention pooling only): multi-head attention pooling, ``classifier.0``
     takes ``heads * feature_dim`` columns; the state_dict keys are the same.  ``attn_dim`` / ``hidden_dim`` are the
-    reference's 128 unless given."""
+    reference's 128 unless given.  ``gated`` (attention pooling only): gated attention, two more keys
+    (``aggregator.attn_G.weight`` [attn_dim][feature_dim], ``aggregator.attn_G.bias`` [attn_dim]); refused together with ``dropout`` > 0."""
 
     def __init__(self, feature_dim, num_classes=2, pooling="attention", dropout=0.0, dropout_seed=0, heads=1, attn_dim=128,
-                 hidden_dim=128):
+                 hidden_dim=128, gated=False):
         super().__init__()
         from .mil_heads import check_heads
 
@@ -107,12 +118,17 @@ class MILClassifier(nn.Module):
         self.heads = check_heads(heads)
         if self.heads != 1 and pooling != "attention":
             raise ValueError(f"heads = {self.heads} needs attention pooling: {pooling} pooling has no attention to branch")
+        self.gated = bool(gated)
+        if self.gated and pooling != "attention":
+            raise ValueError(f"gated = True needs attention pooling: {pooling} pooling has no attention to gate")
+        if self.gated and float(dropout) > 0.0:
+            raise ValueError("gated = True does not go with dropout: the masked step and the Monte-Carlo pass are single-head and ungated")
         self.pooling = pooling
         # plain attributes, not parameters or buffers: the state_dict keeps the reference's keys.  dropout_step is the
         # mask's sample index (the trainer's step number); the caller advances it.
         self.dropout, self.dropout_seed, self.dropout_step = float(dropout), int(dropout_seed), 0
         if pooling == "attention":
-            self.aggregator = MILAttentionPooling(feature_dim, attn_dim, self.heads)
+            self.aggregator = MILAttentionPooling(feature_dim, attn_dim, self.heads, self.gated)
         self.classifier = nn.Sequential(nn.Linear(self.heads * feature_dim, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, num_classes))
 
     def _aggregate(self, bag):
@@ -123,10 +139,15 @@ class MILClassifier(nn.Module):
     def forward_bags(self, feats: torch.Tensor, bag_offsets, want_pooled: bool = False):
         """HIP path for many bags: feats float32[n,F] (bag rows contiguous, on a ROCm device),
         bag_offsets int[n_bags+1] -> (logits[n_bags,C], attn[n] or None[, pooled[n_bags,F]]).  A model of K > 1 heads
-        (the rows of ``aggregator.attn_U.weight``) runs ``hipac_mil_heads_forward``: attn[n,K], pooled[n_bags,K F]."""
+        (the rows of ``aggregator.attn_U.weight``) runs ``hipac_mil_heads_forward``: attn[n,K], pooled[n_bags,K F].  A gated
+        model (one with ``aggregator.attn_G.weight``) runs ``hipac_mil_gated_forward`` for any K: attn[n,K]."""
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         offs = torch.as_tensor(np.asarray(bag_offsets)) if not torch.is_tensor(bag_offsets) else bag_offsets
-        if self.pooling == "attention" and int(sd["aggregator.attn_U.weight"].shape[0]) != 1:
+        if self.pooling == "attention" and "aggregator.attn_G.weight" in sd:
+            from .mil_gated import gated_forward
+
+            logits, attn, pooled = gated_forward(sd, feats.contiguous(), offs, want_pooled=want_pooled)
+        elif self.pooling == "attention" and int(sd["aggregator.attn_U.weight"].shape[0]) != 1:
             from .mil_heads import heads_forward
 
             logits, attn, pooled = heads_forward(sd, feats.contiguous(), offs, want_pooled=want_pooled)

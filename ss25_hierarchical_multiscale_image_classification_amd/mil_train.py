@@ -13,6 +13,9 @@ decay 1e-4, 50 epochs, 32 bags per step, early stopping with patience 5, a 0.8 /
 * Multi-head attention pooling (the yaml's ``attention_heads``, ``--mil_heads K``) comes from ``mil_heads.py``: a model
   whose ``aggregator.attn_U.weight`` has K > 1 rows trains through ``hipac_mil_heads_train_fwd_bwd`` and is scored through
   ``hipac_mil_heads_forward``; one head goes the way it always went.
+* Gated attention (Ilse et al. 2018, eq. 9; ``--mil_gated``) comes from ``mil_gated.py``: a model with the
+  ``aggregator.attn_G`` keys trains through ``hipac_mil_gated_train_fwd_bwd`` and is scored through
+  ``hipac_mil_gated_forward``, for any head count; an ungated model takes exactly the calls it always took.
 * Dropout (the yaml's ``dropout_rate``) and Monte-Carlo dropout uncertainty (its ``uncertainty_estimation``) come from
   ``mil_dropout.py``: the trainer's step under ``hipac_mil_dropout_train_fwd_bwd``, ``predict_mil``'s
   ``results/mil_uncertainty.csv`` from ``mil_dropout.mc_forward``.
@@ -27,7 +30,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import capi, mil_dropout, mil_heads
+from . import capi, mil_dropout, mil_gated, mil_heads
 from .mil import MILClassifier, group_patches_by_wsi
 from .train_native import FlatAdam
 
@@ -61,6 +64,8 @@ PARAM_FIELDS = (("aggregator.attn_V.weight", "attn_V_w"), ("aggregator.attn_V.bi
                 ("aggregator.attn_U.weight", "attn_U_w"), ("aggregator.attn_U.bias", "attn_U_b"),
                 ("classifier.0.weight", "fc1_w"), ("classifier.0.bias", "fc1_b"),
                 ("classifier.2.weight", "fc2_w"), ("classifier.2.bias", "fc2_b"))
+# the gate of a gated model (hipac_mil_gated_params_t's own fields): in the flat buffer after aggregator.attn_U.bias
+GATE_FIELDS = ((mil_gated.GATE_W, "attn_G_w"), (mil_gated.GATE_B, "attn_G_b"))
 
 
 class NativeMILTrainer:
@@ -69,13 +74,20 @@ class NativeMILTrainer:
     16-byte boundary (the gaps stay 0).  ``dropout`` > 0: every forward_backward runs under the masks of
     (``seed``, sample = the number of steps taken so far) -- include/hipac_mil_dropout.h; 0 is the step as it always was.
     The head count is the number of rows of ``aggregator.attn_U.weight``: more than one runs
-    ``hipac_mil_heads_train_fwd_bwd`` (include/hipac_mil_heads.h; not under dropout), one ``hipac_mil_train_fwd_bwd``."""
+    ``hipac_mil_heads_train_fwd_bwd`` (include/hipac_mil_heads.h; not under dropout), one ``hipac_mil_train_fwd_bwd``.
+    A state_dict with the ``aggregator.attn_G`` keys (attention pooling) is a gated model: it runs
+    ``hipac_mil_gated_train_fwd_bwd`` (include/hipac_mil_gated.h; not under dropout) for any head count, the two gate
+    tensors live in the same flat buffer (so Adam and the L2 term cover them) and ``self.attn`` is [n, heads]."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], pooling: str, device, lr: float = 1e-3, weight_decay: float = 1e-4,
                  class_weights=None, dropout: float = 0.0, seed: int = 0):
         if pooling not in capi.MIL_POOLING:
             raise ValueError("Unknown pooling: choose from 'attention', 'mean', 'max'")
         self.keys = [k for k, _ in PARAM_FIELDS if pooling == "attention" or not k.startswith("aggregator.")]
+        self.gated = pooling == "attention" and mil_gated.is_gated(sd)
+        if self.gated:  # the model's own key order: the gate follows aggregator.attn_U
+            at = self.keys.index("aggregator.attn_U.bias") + 1
+            self.keys[at:at] = [k for k, _ in GATE_FIELDS]
         missing = [k for k in self.keys if k not in sd]
         if missing:
             raise capi.HipacError(f"state_dict lacks {missing}")
@@ -83,10 +95,16 @@ class NativeMILTrainer:
         self.dropout, self.seed, self.steps = mil_dropout.check_p(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF, 0
         if self.heads > 1 and self.dropout > 0.0:
             raise ValueError("dropout with more than one attention head is not implemented: the masked step is single-head")
+        if self.gated and self.dropout > 0.0:
+            raise ValueError("dropout with gated attention is not implemented: the masked step is single-head and ungated")
+        if self.gated:
+            mil_gated.gated_dims(sd)  # ValueError if the gate's shapes disagree with attn_V, before anything is loaded
         self.lib = load_mil_train_library()
         if self.dropout > 0.0:
             mil_dropout.load_mil_dropout_library()
-        if self.heads > 1:
+        if self.gated:
+            mil_gated.load_mil_gated_library()
+        elif self.heads > 1:
             mil_heads.load_mil_heads_library()
         self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
         if self.device.type != "cuda":
@@ -121,13 +139,18 @@ class NativeMILTrainer:
         o = self.offsets[key]
         return flat[o:o + int(np.prod(self.shapes[key]))].view(self.shapes[key])
 
-    def _struct(self, flat: torch.Tensor) -> capi.MilParams:
-        p = capi.MilParams()
+    def _struct(self, flat: torch.Tensor):
+        """hipac_mil_params_t over the flat buffer; hipac_mil_gated_params_t (which starts with one) for a gated model."""
+        out = mil_gated.MilGatedParams() if self.gated else capi.MilParams()
+        p = out.base if self.gated else out
         for k, field in PARAM_FIELDS:
             if k in self.offsets:
                 setattr(p, field, flat.data_ptr() + 4 * self.offsets[k])
         p.feature_dim, p.attn_dim, p.hidden_dim, p.num_classes = self.F, self.A, self.hidden, self.C
-        return p
+        if self.gated:
+            for k, field in GATE_FIELDS:
+                setattr(out, field, flat.data_ptr() + 4 * self.offsets[k])
+        return out
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's key names; loads into its MILClassifier and into ``mil.MILClassifier`` with strict=True."""
@@ -141,7 +164,7 @@ class NativeMILTrainer:
         """feats float32[N, F] on the device (stays in place); rows int[n] indices into it, or None for
         the identity (then offsets must end at N); offsets int[n_bags + 1]; labels int64[n_bags] -> (loss float32[], logits[n_bags, C]);
         the gradients land in the flat buffer (``grad_dict``); ``want_attn`` keeps the softmax weights in ``self.attn``
-        ([n], or [n, heads] for more than one head).  Everything is checked on the host before the launch: a
+        ([n], or [n, heads] for more than one head and for a gated model).  Everything is checked on the host before the launch: a
         bad row index never reaches a kernel."""
         if not torch.is_tensor(feats) or not feats.is_cuda:
             raise capi.HipacError("HIP path called with a CPU tensor: there is no CPU fallback (move inputs to cuda)")
@@ -177,7 +200,9 @@ class NativeMILTrainer:
         lab = lab.to(self.device).contiguous()
         offs_dev = torch.from_numpy(offs.astype(np.int32)).to(self.device)
         pool = capi.MIL_POOLING[self.pooling]
-        if self.heads > 1:  # `heads` takes the place of `pooling` in both calls
+        if self.gated:  # `heads` takes the place of `pooling` in both calls
+            pool, query = self.heads, self.lib.hipac_mil_gated_train_workspace_bytes
+        elif self.heads > 1:
             pool, query = self.heads, self.lib.hipac_mil_heads_train_workspace_bytes
         else:
             query = self.lib.hipac_mil_dropout_train_workspace_bytes if self.dropout > 0.0 else self.lib.hipac_mil_train_workspace_bytes
@@ -188,19 +213,21 @@ class NativeMILTrainer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         logits = torch.empty((n_bags, self.C), dtype=torch.float32, device=self.device)
-        self.attn = torch.empty(n if self.heads == 1 else (n, self.heads), dtype=torch.float32, device=self.device) \
+        self.attn = torch.empty(n if self.heads == 1 and not self.gated else (n, self.heads), dtype=torch.float32, device=self.device) \
             if (want_attn and self.pooling == "attention") else None
         args = (C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
                 lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
                 capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0)
         with torch.cuda.device(self.device):
-            if self.heads > 1:
+            if self.gated:
+                rc = self.lib.hipac_mil_gated_train_fwd_bwd(*args, capi._stream())
+            elif self.heads > 1:
                 rc = self.lib.hipac_mil_heads_train_fwd_bwd(*args, capi._stream())
             elif self.dropout > 0.0:
                 rc = self.lib.hipac_mil_dropout_train_fwd_bwd(*args, self.dropout, self.seed, self.steps & 0xFFFFFFFF, capi._stream())
             else:
                 rc = self.lib.hipac_mil_train_fwd_bwd(*args, capi._stream())
-        capi._check(rc, "hipac_mil_heads_train_fwd_bwd" if self.heads > 1 else
+        capi._check(rc, "hipac_mil_gated_train_fwd_bwd" if self.gated else "hipac_mil_heads_train_fwd_bwd" if self.heads > 1 else
                     "hipac_mil_dropout_train_fwd_bwd" if self.dropout > 0.0 else "hipac_mil_train_fwd_bwd")
         return loss, logits
 
@@ -276,12 +303,13 @@ def load_triple(features_path, labels_path, paths_path, by_slide: bool = False):
     return np.ascontiguousarray(feats, dtype=np.float32), order, offsets, names, wsi
 
 
-def initial_state_dict(feature_dim: int, pooling: str, seed: int, heads: int = 1) -> Dict[str, torch.Tensor]:
-    """MILClassifier's own (torch default) initialisation under ``torch.manual_seed(seed)``, drawn on the CPU."""
+def initial_state_dict(feature_dim: int, pooling: str, seed: int, heads: int = 1, gated: bool = False) -> Dict[str, torch.Tensor]:
+    """MILClassifier's own (torch default) initialisation under ``torch.manual_seed(seed)``, drawn on the CPU.  The gate of a
+    gated model is drawn after ``attn_V`` and ``attn_U``."""
     gen_state = torch.get_rng_state()
     torch.manual_seed(seed)
     try:
-        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling, heads=heads).state_dict().items()}
+        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling, heads=heads, gated=gated).state_dict().items()}
     finally:
         torch.set_rng_state(gen_state)
 
@@ -294,10 +322,11 @@ def _gathered(feats_dev: torch.Tensor, bags, order, offsets):
 
 
 def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray, want_attn: bool = False):
-    """The logits of the bags under the model ``sd`` (its head count read from the state_dict); with ``want_attn`` also the
-    attention [n, heads] (None for mean / max pooling)."""
+    """The logits of the bags under the model ``sd`` (its head count and its gate read from the state_dict); with
+    ``want_attn`` also the attention [n, heads] (None for mean / max pooling)."""
     heads = mil_heads.model_dims(sd, pooling)[0]
-    model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling, heads=heads).to(feats.device)
+    gated = pooling == "attention" and mil_gated.is_gated(sd)
+    model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling, heads=heads, gated=gated).to(feats.device)
     model.load_state_dict(sd, strict=True)
     model.eval()
     logits, attn = model.forward_bags(feats, offs)
@@ -309,17 +338,22 @@ def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray, want_attn: bool =
 def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False, epochs: int = 50,
               bags_per_step: int = 32, bag_size: Optional[int] = None, lr: float = 1e-3, weight_decay: float = 1e-4,
               patience: int = 5, seed: int = 0, out_dir: str = ".", max_steps: Optional[int] = None, device=None,
-              dropout: float = 0.0, heads: int = 1) -> Dict[str, object]:
+              dropout: float = 0.0, heads: int = 1, gated: bool = False) -> Dict[str, object]:
     """The yaml's loop (module docstring).  Writes ``<out_dir>/models/mil_model.pth`` (the state with the best validation
     loss; the last one when there is no validation split) and ``<out_dir>/results/metrics.json``; returns the metrics.
     ``dropout`` > 0 trains under dropout (masks seeded by ``seed``); validation and test scoring stay deterministic, and
     the metrics then carry a ``"dropout"`` key.  ``heads`` > 1 (attention pooling, no dropout) trains the multi-head model
-    and the metrics carry ``"attention_heads"``."""
-    dropout, heads = mil_dropout.check_p(dropout), mil_heads.check_heads(heads)
+    and the metrics carry ``"attention_heads"``.  ``gated`` (attention pooling, no dropout, any ``heads``) trains the gated
+    model and the metrics carry ``"gated_attention": true``."""
+    dropout, heads, gated = mil_dropout.check_p(dropout), mil_heads.check_heads(heads), bool(gated)
     if heads > 1 and pooling != "attention":
         raise ValueError(f"heads = {heads} needs attention pooling, not {pooling}")
     if heads > 1 and dropout > 0.0:
         raise ValueError("dropout with more than one attention head is not implemented: the masked step is single-head")
+    if gated and pooling != "attention":
+        raise ValueError(f"gated attention needs attention pooling, not {pooling}")
+    if gated and dropout > 0.0:
+        raise ValueError("dropout with gated attention is not implemented: the masked step is single-head and ungated")
     feats, order, offsets, names, wsi = load_triple(features_path, labels_path, paths_path, by_slide)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     tr, va, te = split_bags(len(names), seed)
@@ -327,8 +361,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
     if len(va) == 0:
         print("[INFO] MIL: the validation split is empty: early stopping is off")
     feats_dev = torch.from_numpy(feats).to(dev)  # uploaded once; every step reads it in place through a row index
-    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed, heads), pooling, dev, lr=lr, weight_decay=weight_decay,
-                               dropout=dropout, seed=seed)
+    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed, heads, gated), pooling, dev, lr=lr,
+                               weight_decay=weight_decay, dropout=dropout, seed=seed)
     labels_all = torch.from_numpy(wsi)
     val = _gathered(feats_dev, va, order, offsets) if len(va) else None
     val_labels = labels_all[torch.from_numpy(va)].to(dev) if len(va) else None
@@ -379,6 +413,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
         metrics["dropout"] = dropout
     if heads > 1:
         metrics["attention_heads"] = heads
+    if gated:
+        metrics["gated_attention"] = True
     with open(os.path.join(out_dir, "results", "metrics.json"), "w") as f:
         json.dump(metrics, f, indent=2)
     print(f"[INFO] MIL: model saved to {model_path}; test accuracy {metrics['accuracy']:.4f}")
@@ -393,7 +429,8 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
     ``<out_dir>/results/mil_uncertainty.csv``: per bag the mean and the variance (divisor T - 1, ``torch.var``) of the
     class-1 probability over ``mc_samples`` stochastic forwards, the entropy of the mean, the mean entropy, their difference
     (the mutual information), and ``mean_probability > threshold`` (the reference's ``softmax_thresholding``).
-    The head count is the saved model's; ``heads``, when given, must agree with it.  ``save_attention`` (attention pooling)
+    The head count is the saved model's; ``heads``, when given, must agree with it.  A gated model (one saved with the
+    ``aggregator.attn_G`` keys) is recognised as such; it has no Monte-Carlo dropout pass.  ``save_attention`` (attention pooling)
     also writes ``<out_dir>/results/mil_attention.npy``: float32 [n, heads], row i the softmax weights of the patch on line
     i of the paths file inside its bag -- what the reference's src/visualization/attention_heatmap.py takes."""
     dropout, mc_samples = mil_dropout.check_p(dropout), int(mc_samples)
@@ -410,6 +447,8 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
         raise ValueError(f"heads = {heads}, but {model_path} has {model_heads} attention head(s)")
     if model_heads > 1 and (dropout > 0.0 or mc_samples > 0):
         raise ValueError("Monte-Carlo dropout with more than one attention head is not implemented: the fused pass is single-head")
+    if pooling == "attention" and mil_gated.is_gated(sd) and (dropout > 0.0 or mc_samples > 0):
+        raise ValueError("Monte-Carlo dropout with gated attention is not implemented: the fused pass is single-head and ungated")
     if save_attention and pooling != "attention":
         raise ValueError(f"save_attention needs attention pooling: {pooling} pooling has no attention weights")
     feats_dev = torch.from_numpy(feats).to(dev)
