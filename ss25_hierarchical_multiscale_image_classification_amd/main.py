@@ -54,6 +54,10 @@ softmaxes over one shared hidden layer, the K pooled vectors concatenated; ``--p
 order of ``patch_paths_L.txt``.
 ``--mil_gated`` trains the gated attention of Ilse et al. 2018 (``mil_gated.py``): a learned sigmoid gate ``aggregator.attn_G``
 over the hidden units, for any ``--mil_heads``; ``--predict_mil`` reads gatedness from the saved model and takes no flag.
+``--mil_levels 1,2,3`` trains the multiscale model (``mil_levels.py``): a slide's bag holds the rows of the triples of all the
+named levels, every level has its own attention branch and softmax, the pooled vectors are concatenated; ``--patch_level`` is
+then not read.  ``--predict_mil`` reads the levels from the saved model; ``--mil_save_attention`` writes one
+``results/mil_attention_<L>.npy`` per level.
 
 Everything else outside the hot path (download, plots) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
@@ -150,6 +154,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--train_mil: gated attention (Ilse et al. 2018, eq. 9; CLAM's form): the score of a patch is "
                         "U (tanh(V x) * sigmoid(G x)), with two more state_dict keys aggregator.attn_G.*.  Attention pooling only, "
                         "any --mil_heads, not with --mil_dropout / --mil_mc_samples.  --predict_mil reads it from the model")
+    p.add_argument("--mil_levels", type=str, default=None, metavar="L,L,...",
+                   help="--train_mil over several pyramid levels: two to four distinct levels out of 0..3, ascending, such as 1,2,3. "
+                        "A slide's bag holds the rows of all of them, every level has its own attention branch and softmax; "
+                        "--patch_level is ignored.  Attention pooling only, not with --mil_heads > 1, --mil_gated, --mil_dropout / "
+                        "--mil_mc_samples.  --predict_mil reads the levels from the model; if given they must agree")
     p.add_argument("--mil_save_attention", action="store_true",
                    help="--predict_mil with attention pooling: also write results/mil_attention.npy, float32 [patches, K], row i "
                         "= the attention weights of line i of patch_paths_L.txt inside its bag")
@@ -527,11 +536,77 @@ def check_mil_args(parser, args):
         if args.mil_dropout > 0.0 or args.mil_mc_samples > 0:
             parser.error("--mil_gated with --mil_dropout / --mil_mc_samples is not implemented: the dropout step and the "
                          "Monte-Carlo pass are single-head and ungated")
+    if args.mil_levels is not None:
+        from .mil_levels import parse_levels_flag
+
+        try:
+            args.mil_levels = parse_levels_flag(args.mil_levels)
+        except ValueError as e:
+            parser.error(str(e))
+        if args.mil_pooling != "attention":
+            parser.error(f"--mil_levels needs --mil_pooling attention: {args.mil_pooling} pooling has no attention branch per level")
+        if heads is not None and heads > 1:
+            parser.error(f"--mil_levels with --mil_heads {heads} is not implemented: every level has one attention branch")
+        if args.mil_gated:
+            parser.error("--mil_levels with --mil_gated is not implemented: the branches of the levels are ungated")
+        if args.mil_dropout > 0.0 or args.mil_mc_samples > 0:
+            parser.error("--mil_levels with --mil_dropout / --mil_mc_samples is not implemented: the dropout step and the "
+                         "Monte-Carlo pass are single-scale")
     if args.mil_save_attention and args.mil_pooling != "attention":
         parser.error(f"--mil_save_attention needs --mil_pooling attention: {args.mil_pooling} pooling has no attention weights")
 
 
+def mil_model_levels(args):
+    """The pyramid levels of the saved model of --predict_mil when it is a levels model (read on the host), else None."""
+    if args.mil_pooling != "attention" or not os.path.exists(args.mil_model):
+        return None
+    from .mil_levels import LEVELS_KEY, model_levels
+
+    try:
+        sd = torch.load(args.mil_model, map_location="cpu", weights_only=True)
+    except Exception:  # not a readable state_dict: the single-level path says so as it always did
+        return None
+    return model_levels(sd) if isinstance(sd, dict) and LEVELS_KEY in sd else None  # ValueError: the buffer against attn_U
+
+
+def cmd_mil_levels(args, train: bool, levels):
+    """--train_mil --mil_levels, and --predict_mil with a model trained that way: the triples of all its levels."""
+    from .mil_levels import triple_names
+
+    missing = [(level, f) for level in levels for f in triple_names(level) if not os.path.exists(f)]
+    if missing:
+        print(f"[ERROR] {', '.join(f for _, f in missing)} not found: run --extract_features --patch_level L for L in "
+              f"{','.join(str(v) for v in sorted({v for v, _ in missing}))} first.")
+        return 2
+    from .dist import rank_world
+
+    if rank_world()[0] != 0:  # not sharded: rank 0 does it
+        return 0
+    from . import mil_train
+
+    seed = 0 if args.seed is None else args.seed
+    try:
+        if train:
+            mil_train.train_mil(None, None, None, pooling="attention", epochs=args.mil_epochs, bags_per_step=args.mil_bags_per_step,
+                                bag_size=args.mil_bag_size, seed=seed, max_steps=args.max_steps, levels=levels)
+        else:
+            mil_train.predict_mil(args.mil_model, None, None, None, pooling="attention", seed=seed, heads=args.mil_heads,
+                                  save_attention=args.mil_save_attention, levels=args.mil_levels, dropout=args.mil_dropout,
+                                  mc_samples=args.mil_mc_samples)
+    except ValueError as e:  # differing feature dims; the model's levels against the flags
+        print(f"[ERROR] --{'train_mil' if train else 'predict_mil'}: {e}")
+        return 2
+    return 0
+
+
 def cmd_mil(args, train: bool):
+    try:
+        levels = args.mil_levels if train else mil_model_levels(args)
+    except ValueError as e:  # a levels model whose buffer disagrees with its attention branches
+        print(f"[ERROR] --predict_mil: {args.mil_model}: {e}")
+        return 2
+    if levels is not None:
+        return cmd_mil_levels(args, train, levels)
     triple = mil_triple(args)  # before anything touches a GPU
     if triple is None:
         return 2
@@ -563,7 +638,7 @@ def cmd_mil(args, train: bool):
     try:
         mil_train.predict_mil(args.mil_model, *triple, pooling=args.mil_pooling, by_slide=args.mil_by_slide, dropout=args.mil_dropout,
                               mc_samples=args.mil_mc_samples, threshold=args.mil_threshold, seed=0 if args.seed is None else args.seed,
-                              heads=args.mil_heads, save_attention=args.mil_save_attention)
+                              heads=args.mil_heads, save_attention=args.mil_save_attention, levels=args.mil_levels)
     except ValueError as e:  # the model's head count or its gate against the flags
         print(f"[ERROR] --predict_mil: {e}")
         return 2
@@ -587,7 +662,7 @@ def main(argv=None) -> int:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")
             return 2
-    if (args.train_mil or args.predict_mil) and args.patch_level == "all":
+    if (args.train_mil or args.predict_mil) and args.patch_level == "all" and args.mil_levels is None:
         mil_triple(args)  # prints why; refused before any process is started or any GPU touched
         return 2
     if args.detect and detect_geometry(args) is None:  # refused before any process is started or any GPU touched

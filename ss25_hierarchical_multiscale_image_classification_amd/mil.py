@@ -14,6 +14,10 @@
   ``attn_G = Linear(in_dim, attn_dim)`` (keys ``aggregator.attn_G.weight`` / ``.bias``, constructed last, so an ungated model
   draws the same numbers and has the same keys as before) and scores a patch with ``attn_U(tanh(attn_V(x)) * sigmoid(attn_G(x)))``;
   ``eval()`` runs ``hipac_mil_gated_forward`` (``mil_gated.py``) for any K.  A saved model is gated if it has the keys.
+  ``levels=(1, 2, 3)`` is the multiscale model of ``mil_levels.py``: a bag holds rows of L pyramid levels, ``attn_U`` has one
+  branch per level and every level its own softmax over its rows of the bag; the shapes are those of ``heads=L``, plus the
+  registered buffer ``aggregator.levels`` (int64[L]) by which a saved model is recognised.  ``forward`` / ``forward_bags`` then
+  take ``level_of`` (the level slot of every row); a GPU tensor runs ``hipac_mil_levels_forward``, a CPU tensor plain torch.
 * ``group_patches_by_wsi`` / ``WSIMILDDataset`` -- src/datasets/mildataset.py:6-47.  By default the
   bag key is the reference's as written: ``'_'.join(basename.split('_')[:-2])``, which for the patch
   names ``{slide}_x{x}_y{y}_{label}.png`` keeps the ``_x{x}`` field (one bag per slide COLUMN);
@@ -78,9 +82,10 @@ class MILAttentionPooling(nn.Module):
     (the yaml's ``attention_heads``): ``attn_U`` is ``Linear(attn_dim, K)``, the softmax runs per head over the bag, and
     ``forward`` returns the K pooled vectors concatenated head-major (K * in_dim) and the attention (N, K).  K = 1 is
     the reference's module.  ``gated``: the score is ``attn_U(tanh(attn_V(x)) * sigmoid(attn_G(x)))`` (Ilse et al. eq. 9);
-    ``attn_G`` is constructed after the other two, and only then."""
+    ``attn_G`` is constructed after the other two, and only then.  ``levels`` (pyramid levels, ascending): one branch per
+    level (``heads`` = their number) and the buffer ``levels``; ``forward`` then needs ``level_of``."""
 
-    def __init__(self, in_dim, attn_dim=128, heads=1, gated=False):
+    def __init__(self, in_dim, attn_dim=128, heads=1, gated=False, levels=None):
         super().__init__()
         from .mil_heads import check_heads
 
@@ -89,6 +94,8 @@ class MILAttentionPooling(nn.Module):
         self.attn_U = nn.Linear(attn_dim, self.heads)
         if self.gated:
             self.attn_G = nn.Linear(in_dim, attn_dim)
+        if levels is not None:
+            self.register_buffer("levels", torch.tensor(list(levels), dtype=torch.int64))
 
     def forward(self, x):
         if self.gated:
@@ -104,10 +111,12 @@ class MILClassifier(nn.Module):
     """mil_classifier.py:20-45.  ``heads`` > 1 (attention pooling only): multi-head attention pooling, ``classifier.0``
     takes ``heads * feature_dim`` columns; the state_dict keys are the same.  ``attn_dim`` / ``hidden_dim`` are the
     reference's 128 unless given.  ``gated`` (attention pooling only): gated attention, two more keys
-    (``aggregator.attn_G.weight`` [attn_dim][feature_dim], ``aggregator.attn_G.bias`` [attn_dim]); refused together with ``dropout`` > 0."""
+    (``aggregator.attn_G.weight`` [attn_dim][feature_dim], ``aggregator.attn_G.bias`` [attn_dim]); refused together with ``dropout`` > 0.
+    ``levels`` (attention pooling only; not with ``heads`` > 1, ``gated`` or ``dropout``): the multiscale model of
+    ``mil_levels.py`` over these pyramid levels, in the shapes of ``heads = len(levels)`` plus the buffer ``aggregator.levels``."""
 
     def __init__(self, feature_dim, num_classes=2, pooling="attention", dropout=0.0, dropout_seed=0, heads=1, attn_dim=128,
-                 hidden_dim=128, gated=False):
+                 hidden_dim=128, gated=False, levels=None):
         super().__init__()
         from .mil_heads import check_heads
 
@@ -123,12 +132,22 @@ class MILClassifier(nn.Module):
             raise ValueError(f"gated = True needs attention pooling: {pooling} pooling has no attention to gate")
         if self.gated and float(dropout) > 0.0:
             raise ValueError("gated = True does not go with dropout: the masked step and the Monte-Carlo pass are single-head and ungated")
+        self.levels = None
+        if levels is not None:
+            from .mil_levels import check_levels
+
+            self.levels = check_levels(levels)
+            if pooling != "attention":
+                raise ValueError(f"levels needs attention pooling: {pooling} pooling has no attention branch per level")
+            if self.heads != 1 or self.gated or float(dropout) > 0.0:
+                raise ValueError("levels does not go with heads > 1, gated = True or dropout: every level has one ungated branch")
+            self.heads = len(self.levels)
         self.pooling = pooling
         # plain attributes, not parameters or buffers: the state_dict keeps the reference's keys.  dropout_step is the
         # mask's sample index (the trainer's step number); the caller advances it.
         self.dropout, self.dropout_seed, self.dropout_step = float(dropout), int(dropout_seed), 0
         if pooling == "attention":
-            self.aggregator = MILAttentionPooling(feature_dim, attn_dim, self.heads, self.gated)
+            self.aggregator = MILAttentionPooling(feature_dim, attn_dim, self.heads, self.gated, self.levels)
         self.classifier = nn.Sequential(nn.Linear(self.heads * feature_dim, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, num_classes))
 
     def _aggregate(self, bag):
@@ -136,14 +155,26 @@ class MILClassifier(nn.Module):
             return self.aggregator(bag)
         return (bag.mean(dim=0), None) if self.pooling == "mean" else (bag.max(dim=0)[0], None)
 
-    def forward_bags(self, feats: torch.Tensor, bag_offsets, want_pooled: bool = False):
+    def forward_bags(self, feats: torch.Tensor, bag_offsets, want_pooled: bool = False, level_of=None):
         """HIP path for many bags: feats float32[n,F] (bag rows contiguous, on a ROCm device),
         bag_offsets int[n_bags+1] -> (logits[n_bags,C], attn[n] or None[, pooled[n_bags,F]]).  A model of K > 1 heads
         (the rows of ``aggregator.attn_U.weight``) runs ``hipac_mil_heads_forward``: attn[n,K], pooled[n_bags,K F].  A gated
-        model (one with ``aggregator.attn_G.weight``) runs ``hipac_mil_gated_forward`` for any K: attn[n,K]."""
+        model (one with ``aggregator.attn_G.weight``) runs ``hipac_mil_gated_forward`` for any K: attn[n,K].  A levels model
+        (one with ``aggregator.levels``) needs ``level_of`` int[n], the level slot of every row, and gives attn[n],
+        pooled[n_bags,L F]: ``hipac_mil_levels_forward`` on a GPU tensor, ``mil_levels.host_forward`` (plain torch, differentiable)
+        on a CPU tensor.  Any other model refuses ``level_of``."""
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         offs = torch.as_tensor(np.asarray(bag_offsets)) if not torch.is_tensor(bag_offsets) else bag_offsets
-        if self.pooling == "attention" and "aggregator.attn_G.weight" in sd:
+        if (level_of is not None) != ("aggregator.levels" in sd):
+            raise ValueError("level_of goes with a levels model (one with aggregator.levels), and such a model needs it")
+        if level_of is not None:
+            from .mil_levels import host_forward, levels_forward
+
+            if torch.is_tensor(feats) and not feats.is_cuda:
+                logits, attn, pooled = host_forward(self, feats, offs, level_of)
+            else:
+                logits, attn, pooled = levels_forward(sd, feats.contiguous(), offs, level_of, want_pooled=want_pooled)
+        elif self.pooling == "attention" and "aggregator.attn_G.weight" in sd:
             from .mil_gated import gated_forward
 
             logits, attn, pooled = gated_forward(sd, feats.contiguous(), offs, want_pooled=want_pooled)
@@ -155,10 +186,21 @@ class MILClassifier(nn.Module):
             logits, attn, pooled = capi.mil_forward(sd, self.pooling, feats.contiguous(), offs, want_pooled=want_pooled)
         return (logits, attn, pooled) if want_pooled else (logits, attn)
 
-    def forward(self, bag, row0=0, bag_index=0):
+    def forward(self, bag, row0=0, bag_index=0, level_of=None):
         """bag: (num_patches, feature_dim) -> (logits (num_classes), attention (num_patches, heads) or None).  ``row0`` (the
         position of the bag's first row in the batch) and ``bag_index`` place the bag in the dropout masks; they matter in
-        ``train()`` mode with ``dropout > 0`` only."""
+        ``train()`` mode with ``dropout > 0`` only.  A levels model needs ``level_of`` (see ``forward_bags``); its attention is
+        (num_patches, 1), and in ``train()`` mode it runs ``mil_levels.host_forward``."""
+        if self.levels is not None:
+            if self.training:
+                from .mil_levels import host_forward
+
+                logits, attn, _ = host_forward(self, bag, [0, bag.shape[0]], level_of)
+            else:
+                logits, attn = self.forward_bags(bag, torch.tensor([0, bag.shape[0]]), level_of=level_of)
+            return logits[0], attn.reshape(bag.shape[0], 1)
+        if level_of is not None:
+            raise ValueError("level_of goes with a levels model (one with aggregator.levels)")
         if self.training:
             if self.dropout > 0.0:
                 from .mil_dropout import host_dropout

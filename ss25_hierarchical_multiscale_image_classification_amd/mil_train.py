@@ -16,6 +16,9 @@ decay 1e-4, 50 epochs, 32 bags per step, early stopping with patience 5, a 0.8 /
 * Gated attention (Ilse et al. 2018, eq. 9; ``--mil_gated``) comes from ``mil_gated.py``: a model with the
   ``aggregator.attn_G`` keys trains through ``hipac_mil_gated_train_fwd_bwd`` and is scored through
   ``hipac_mil_gated_forward``, for any head count; an ungated model takes exactly the calls it always took.
+* Multiscale bags (``--mil_levels 1,2,3``) come from ``mil_levels.py``: a model with the ``aggregator.levels`` buffer trains
+  through ``hipac_mil_levels_train_fwd_bwd`` and is scored through ``hipac_mil_levels_forward`` over the triples of all its
+  levels, with one attention branch and one softmax per level; any other model takes exactly the calls it always took.
 * Dropout (the yaml's ``dropout_rate``) and Monte-Carlo dropout uncertainty (its ``uncertainty_estimation``) come from
   ``mil_dropout.py``: the trainer's step under ``hipac_mil_dropout_train_fwd_bwd``, ``predict_mil``'s
   ``results/mil_uncertainty.csv`` from ``mil_dropout.mc_forward``.
@@ -30,7 +33,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import capi, mil_dropout, mil_gated, mil_heads
+from . import capi, mil_dropout, mil_gated, mil_heads, mil_levels
 from .mil import MILClassifier, group_patches_by_wsi
 from .train_native import FlatAdam
 
@@ -77,7 +80,10 @@ class NativeMILTrainer:
     ``hipac_mil_heads_train_fwd_bwd`` (include/hipac_mil_heads.h; not under dropout), one ``hipac_mil_train_fwd_bwd``.
     A state_dict with the ``aggregator.attn_G`` keys (attention pooling) is a gated model: it runs
     ``hipac_mil_gated_train_fwd_bwd`` (include/hipac_mil_gated.h; not under dropout) for any head count, the two gate
-    tensors live in the same flat buffer (so Adam and the L2 term cover them) and ``self.attn`` is [n, heads]."""
+    tensors live in the same flat buffer (so Adam and the L2 term cover them) and ``self.attn`` is [n, heads].
+    A state_dict with the ``aggregator.levels`` buffer (attention pooling, ungated, no dropout) is a levels model: it runs
+    ``hipac_mil_levels_train_fwd_bwd`` (include/hipac_mil_levels.h), ``forward_backward`` / ``step`` then need ``level_of``,
+    ``self.attn`` is [n], and ``state_dict`` carries the buffer along."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], pooling: str, device, lr: float = 1e-3, weight_decay: float = 1e-4,
                  class_weights=None, dropout: float = 0.0, seed: int = 0):
@@ -92,7 +98,10 @@ class NativeMILTrainer:
         if missing:
             raise capi.HipacError(f"state_dict lacks {missing}")
         self.heads = mil_heads.model_dims(sd, pooling)[0]  # ValueError if classifier.0.weight disagrees with heads * feature_dim
+        self.levels = mil_levels.model_levels(sd) if pooling == "attention" else None  # ValueError if it disagrees with attn_U
         self.dropout, self.seed, self.steps = mil_dropout.check_p(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        if self.levels is not None and (self.gated or self.dropout > 0.0):
+            raise ValueError("a levels model is ungated and trains without dropout: every level has one plain attention branch")
         if self.heads > 1 and self.dropout > 0.0:
             raise ValueError("dropout with more than one attention head is not implemented: the masked step is single-head")
         if self.gated and self.dropout > 0.0:
@@ -104,6 +113,8 @@ class NativeMILTrainer:
             mil_dropout.load_mil_dropout_library()
         if self.gated:
             mil_gated.load_mil_gated_library()
+        elif self.levels is not None:
+            mil_levels.load_mil_levels_library()
         elif self.heads > 1:
             mil_heads.load_mil_heads_library()
         self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
@@ -154,18 +165,24 @@ class NativeMILTrainer:
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's key names; loads into its MILClassifier and into ``mil.MILClassifier`` with strict=True."""
-        return {k: self._view(self.opt.params, k).clone() for k in self.keys}
+        out = {k: self._view(self.opt.params, k).clone() for k in self.keys}
+        if self.levels is not None:
+            out[mil_levels.LEVELS_KEY] = torch.tensor(self.levels, dtype=torch.int64, device=self.device)
+        return out
 
     def grad_dict(self) -> Dict[str, torch.Tensor]:
         return {k: self._view(self.opt.grads, k).clone() for k in self.keys}
 
-    def forward_backward(self, feats: torch.Tensor, rows, offsets, labels, accumulate: bool = False, want_attn: bool = False
-                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    def forward_backward(self, feats: torch.Tensor, rows, offsets, labels, accumulate: bool = False, want_attn: bool = False,
+                         level_of=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """feats float32[N, F] on the device (stays in place); rows int[n] indices into it, or None for
         the identity (then offsets must end at N); offsets int[n_bags + 1]; labels int64[n_bags] -> (loss float32[], logits[n_bags, C]);
         the gradients land in the flat buffer (``grad_dict``); ``want_attn`` keeps the softmax weights in ``self.attn``
-        ([n], or [n, heads] for more than one head and for a gated model).  Everything is checked on the host before the launch: a
-        bad row index never reaches a kernel."""
+        ([n], or [n, heads] for more than one head and for a gated model).  ``level_of`` int[n]: the level slot of every BATCH
+        row, for a levels model and only for one (ValueError otherwise); ``self.attn`` is then [n].  Everything is checked on
+        the host before the launch: a bad row index never reaches a kernel."""
+        if (level_of is not None) != (self.levels is not None):
+            raise ValueError("level_of goes with a levels model (one with aggregator.levels), and such a model needs it")
         if not torch.is_tensor(feats) or not feats.is_cuda:
             raise capi.HipacError("HIP path called with a CPU tensor: there is no CPU fallback (move inputs to cuda)")
         if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous() or feats.device != self.device:
@@ -199,8 +216,11 @@ class NativeMILTrainer:
             raise capi.HipacError(f"labels holds a class outside [0, {self.C})")
         lab = lab.to(self.device).contiguous()
         offs_dev = torch.from_numpy(offs.astype(np.int32)).to(self.device)
+        lv_dev = None if level_of is None else mil_levels._check_level_of(level_of, n).to(self.device, torch.uint8).contiguous()
         pool = capi.MIL_POOLING[self.pooling]
-        if self.gated:  # `heads` takes the place of `pooling` in both calls
+        if self.levels is not None:  # `levels` takes the place of `pooling` in both calls
+            pool, query = self.heads, self.lib.hipac_mil_levels_train_workspace_bytes
+        elif self.gated:  # `heads` takes the place of `pooling` in both calls
             pool, query = self.heads, self.lib.hipac_mil_gated_train_workspace_bytes
         elif self.heads > 1:
             pool, query = self.heads, self.lib.hipac_mil_heads_train_workspace_bytes
@@ -213,13 +233,16 @@ class NativeMILTrainer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         logits = torch.empty((n_bags, self.C), dtype=torch.float32, device=self.device)
-        self.attn = torch.empty(n if self.heads == 1 and not self.gated else (n, self.heads), dtype=torch.float32, device=self.device) \
+        one = (self.heads == 1 and not self.gated) or self.levels is not None
+        self.attn = torch.empty(n if one else (n, self.heads), dtype=torch.float32, device=self.device) \
             if (want_attn and self.pooling == "attention") else None
         args = (C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
                 lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
                 capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0)
         with torch.cuda.device(self.device):
-            if self.gated:
+            if self.levels is not None:  # level_of goes in after rows
+                rc = self.lib.hipac_mil_levels_train_fwd_bwd(*args[:5], lv_dev.data_ptr(), *args[5:], capi._stream())
+            elif self.gated:
                 rc = self.lib.hipac_mil_gated_train_fwd_bwd(*args, capi._stream())
             elif self.heads > 1:
                 rc = self.lib.hipac_mil_heads_train_fwd_bwd(*args, capi._stream())
@@ -227,13 +250,13 @@ class NativeMILTrainer:
                 rc = self.lib.hipac_mil_dropout_train_fwd_bwd(*args, self.dropout, self.seed, self.steps & 0xFFFFFFFF, capi._stream())
             else:
                 rc = self.lib.hipac_mil_train_fwd_bwd(*args, capi._stream())
-        capi._check(rc, "hipac_mil_gated_train_fwd_bwd" if self.gated else "hipac_mil_heads_train_fwd_bwd" if self.heads > 1 else
+        capi._check(rc, "hipac_mil_levels_train_fwd_bwd" if self.levels is not None else "hipac_mil_gated_train_fwd_bwd" if self.gated else "hipac_mil_heads_train_fwd_bwd" if self.heads > 1 else
                     "hipac_mil_dropout_train_fwd_bwd" if self.dropout > 0.0 else "hipac_mil_train_fwd_bwd")
         return loss, logits
 
-    def step(self, feats, rows, offsets, labels) -> Tuple[torch.Tensor, torch.Tensor]:
+    def step(self, feats, rows, offsets, labels, level_of=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """forward_backward, the L2 term (g += weight_decay * p, torch-Adam's form), one Adam update."""
-        loss, logits = self.forward_backward(feats, rows, offsets, labels)
+        loss, logits = self.forward_backward(feats, rows, offsets, labels, level_of=level_of)
         if self.weight_decay != 0.0:
             with torch.cuda.device(self.device):
                 capi._check(self.lib.hipac_mil_train_l2_add(self.opt.grads.data_ptr(), self.opt.params.data_ptr(),
@@ -303,13 +326,15 @@ def load_triple(features_path, labels_path, paths_path, by_slide: bool = False):
     return np.ascontiguousarray(feats, dtype=np.float32), order, offsets, names, wsi
 
 
-def initial_state_dict(feature_dim: int, pooling: str, seed: int, heads: int = 1, gated: bool = False) -> Dict[str, torch.Tensor]:
+def initial_state_dict(feature_dim: int, pooling: str, seed: int, heads: int = 1, gated: bool = False, levels=None
+                       ) -> Dict[str, torch.Tensor]:
     """MILClassifier's own (torch default) initialisation under ``torch.manual_seed(seed)``, drawn on the CPU.  The gate of a
-    gated model is drawn after ``attn_V`` and ``attn_U``."""
+    gated model is drawn after ``attn_V`` and ``attn_U``.  ``levels``: a levels model, with its ``aggregator.levels`` buffer."""
     gen_state = torch.get_rng_state()
     torch.manual_seed(seed)
     try:
-        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling, heads=heads, gated=gated).state_dict().items()}
+        return {k: v.detach().clone() for k, v in MILClassifier(feature_dim, 2, pooling, heads=heads, gated=gated,
+                                                                  levels=levels).state_dict().items()}
     finally:
         torch.set_rng_state(gen_state)
 
@@ -321,9 +346,22 @@ def _gathered(feats_dev: torch.Tensor, bags, order, offsets):
     return feats_dev[torch.from_numpy(rows).to(feats_dev.device)].contiguous(), offs
 
 
-def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray, want_attn: bool = False):
+def _gathered_levels(level_rows: np.ndarray, bags, order, offsets) -> np.ndarray:
+    """The level slots of the rows ``_gathered`` copies, in its order."""
+    return np.ascontiguousarray(level_rows[np.concatenate([order[offsets[b]:offsets[b + 1]] for b in bags])], dtype=np.uint8)
+
+
+def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray, want_attn: bool = False, level_of=None):
     """The logits of the bags under the model ``sd`` (its head count and its gate read from the state_dict); with
-    ``want_attn`` also the attention [n, heads] (None for mean / max pooling)."""
+    ``want_attn`` also the attention [n, heads] (None for mean / max pooling).  ``level_of``: the level slots of the rows, for a
+    levels model (one with ``aggregator.levels``) and only for one; its attention is [n, 1]."""
+    if level_of is not None:
+        model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling,
+                              levels=mil_levels.model_levels(sd)).to(feats.device)
+        model.load_state_dict(sd, strict=True)
+        model.eval()
+        logits, attn = model.forward_bags(feats, offs, level_of=level_of)
+        return (logits, attn.reshape(feats.shape[0], 1)) if want_attn else logits
     heads = mil_heads.model_dims(sd, pooling)[0]
     gated = pooling == "attention" and mil_gated.is_gated(sd)
     model = MILClassifier(feats.shape[1], int(sd["classifier.2.weight"].shape[0]), pooling, heads=heads, gated=gated).to(feats.device)
@@ -338,14 +376,21 @@ def _score(sd, pooling, feats: torch.Tensor, offs: np.ndarray, want_attn: bool =
 def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False, epochs: int = 50,
               bags_per_step: int = 32, bag_size: Optional[int] = None, lr: float = 1e-3, weight_decay: float = 1e-4,
               patience: int = 5, seed: int = 0, out_dir: str = ".", max_steps: Optional[int] = None, device=None,
-              dropout: float = 0.0, heads: int = 1, gated: bool = False) -> Dict[str, object]:
+              dropout: float = 0.0, heads: int = 1, gated: bool = False, levels=None, data_dir: str = ".") -> Dict[str, object]:
     """The yaml's loop (module docstring).  Writes ``<out_dir>/models/mil_model.pth`` (the state with the best validation
     loss; the last one when there is no validation split) and ``<out_dir>/results/metrics.json``; returns the metrics.
     ``dropout`` > 0 trains under dropout (masks seeded by ``seed``); validation and test scoring stay deterministic, and
     the metrics then carry a ``"dropout"`` key.  ``heads`` > 1 (attention pooling, no dropout) trains the multi-head model
     and the metrics carry ``"attention_heads"``.  ``gated`` (attention pooling, no dropout, any ``heads``) trains the gated
-    model and the metrics carry ``"gated_attention": true``."""
+    model and the metrics carry ``"gated_attention": true``.  ``levels`` (two or more pyramid levels, ascending; attention
+    pooling, one head, ungated, no dropout) trains the multiscale model of ``mil_levels.py``: the three paths are not read
+    (give None), the bags are those of ``mil_levels.load_triples(levels, data_dir)`` (one per slide, whatever ``by_slide``
+    says), ``bag_size`` samples per (bag, level), and the metrics carry ``"levels"``."""
     dropout, heads, gated = mil_dropout.check_p(dropout), mil_heads.check_heads(heads), bool(gated)
+    if levels is not None:
+        levels = mil_levels.check_levels(levels)
+        if pooling != "attention" or heads > 1 or gated or dropout > 0.0:
+            raise ValueError("levels needs attention pooling with one head per level, ungated and without dropout")
     if heads > 1 and pooling != "attention":
         raise ValueError(f"heads = {heads} needs attention pooling, not {pooling}")
     if heads > 1 and dropout > 0.0:
@@ -354,24 +399,32 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
         raise ValueError(f"gated attention needs attention pooling, not {pooling}")
     if gated and dropout > 0.0:
         raise ValueError("dropout with gated attention is not implemented: the masked step is single-head and ungated")
-    feats, order, offsets, names, wsi = load_triple(features_path, labels_path, paths_path, by_slide)
+    if levels is None:
+        feats, order, offsets, names, wsi = load_triple(features_path, labels_path, paths_path, by_slide)
+        level_rows = None
+    else:
+        feats, level_rows, order, offsets, names, wsi, _ = mil_levels.load_triples(levels, data_dir)
+    lv = (lambda bags: {}) if levels is None else (lambda bags: {"level_of": _gathered_levels(level_rows, bags, order, offsets)})
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     tr, va, te = split_bags(len(names), seed)
     print(f"[INFO] MIL: {len(names)} bags of {feats.shape[0]} patches; train / val / test = {len(tr)} / {len(va)} / {len(te)}")
     if len(va) == 0:
         print("[INFO] MIL: the validation split is empty: early stopping is off")
     feats_dev = torch.from_numpy(feats).to(dev)  # uploaded once; every step reads it in place through a row index
-    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed, heads, gated), pooling, dev, lr=lr,
+    trainer = NativeMILTrainer(initial_state_dict(feats.shape[1], pooling, seed, heads, gated, levels), pooling, dev, lr=lr,
                                weight_decay=weight_decay, dropout=dropout, seed=seed)
     labels_all = torch.from_numpy(wsi)
     val = _gathered(feats_dev, va, order, offsets) if len(va) else None
     val_labels = labels_all[torch.from_numpy(va)].to(dev) if len(va) else None
+    val_lv = lv(va) if len(va) else {}
     history = {"train_loss": [], "val_loss": []}
     best, best_sd, bad, steps, stopped = float("inf"), None, 0, 0, False
     for epoch in range(epochs):
         losses = []
-        for rows, offs, group in epoch_batches(tr, order, offsets, epoch, seed, bags_per_step, bag_size):
-            loss, _ = trainer.step(feats_dev, rows, offs, labels_all[torch.from_numpy(group)])
+        batches = epoch_batches(tr, order, offsets, epoch, seed, bags_per_step, bag_size) if levels is None else \
+            mil_levels.epoch_batches(tr, order, offsets, level_rows, len(levels), epoch, seed, bags_per_step, bag_size)
+        for rows, offs, group, *batch_lv in batches:  # a levels batch carries the level slots of its rows
+            loss, _ = trainer.step(feats_dev, rows, offs, labels_all[torch.from_numpy(group)], *batch_lv)
             losses.append(loss)
             steps += 1
             if max_steps is not None and steps >= max_steps:
@@ -379,7 +432,7 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
         history["train_loss"].append(float(torch.stack(losses).mean().item()))
         msg = f"[INFO] MIL epoch {epoch + 1}/{epochs}: train loss {history['train_loss'][-1]:.6f}"
         if val is not None:
-            v = float(torch.nn.functional.cross_entropy(_score(trainer.state_dict(), pooling, *val), val_labels).item())
+            v = float(torch.nn.functional.cross_entropy(_score(trainer.state_dict(), pooling, *val, **val_lv), val_labels).item())
             history["val_loss"].append(v)
             msg += f", val loss {v:.6f}"
             if v < best:
@@ -401,7 +454,7 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
     torch.save({k: v.cpu() for k, v in best_sd.items()}, model_path)
     if len(te):
         tf, toffs = _gathered(feats_dev, te, order, offsets)
-        pred = _score(best_sd, pooling, tf, toffs).argmax(1).cpu().numpy()
+        pred = _score(best_sd, pooling, tf, toffs, **lv(te)).argmax(1).cpu().numpy()
         metrics = classification_metrics(wsi[te], pred)
     else:
         print("[INFO] MIL: the test split is empty: the metrics are those of no predictions")
@@ -415,6 +468,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
         metrics["attention_heads"] = heads
     if gated:
         metrics["gated_attention"] = True
+    if levels is not None:
+        metrics["levels"] = [int(v) for v in levels]
     with open(os.path.join(out_dir, "results", "metrics.json"), "w") as f:
         json.dump(metrics, f, indent=2)
     print(f"[INFO] MIL: model saved to {model_path}; test accuracy {metrics['accuracy']:.4f}")
@@ -423,7 +478,8 @@ def train_mil(features_path, labels_path, paths_path, *, pooling: str = "attenti
 
 def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: str = "attention", by_slide: bool = False,
                 out_dir: str = ".", device=None, dropout: float = 0.0, mc_samples: int = 0, threshold: float = 0.5, seed: int = 0,
-                heads: Optional[int] = None, save_attention: bool = False) -> List[Tuple[str, float, int]]:
+                heads: Optional[int] = None, save_attention: bool = False, levels=None, data_dir: str = "."
+                ) -> List[Tuple[str, float, int]]:
     """Every bag of the triple scored with a saved model -> [(bag name, probability of class 1, predicted label)], also
     written as ``<out_dir>/results/mil_predictions.csv``.  With ``mc_samples`` > 0 (needs ``dropout`` > 0) it also writes
     ``<out_dir>/results/mil_uncertainty.csv``: per bag the mean and the variance (divisor T - 1, ``torch.var``) of the
@@ -432,16 +488,36 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
     The head count is the saved model's; ``heads``, when given, must agree with it.  A gated model (one saved with the
     ``aggregator.attn_G`` keys) is recognised as such; it has no Monte-Carlo dropout pass.  ``save_attention`` (attention pooling)
     also writes ``<out_dir>/results/mil_attention.npy``: float32 [n, heads], row i the softmax weights of the patch on line
-    i of the paths file inside its bag -- what the reference's src/visualization/attention_heatmap.py takes."""
+    i of the paths file inside its bag -- what the reference's src/visualization/attention_heatmap.py takes.
+    A levels model (one saved with the ``aggregator.levels`` buffer) is scored with ``features_path`` = None: the triples of
+    the model's own levels are read from ``data_dir`` (``mil_levels.load_triples``), one bag per slide; ``levels``, when given,
+    must agree with the model.  ``save_attention`` then writes ``<out_dir>/results/mil_attention_<L>.npy`` per level, float32
+    [patches_L, 1], row i the weight of the patch on line i of ``patch_paths_<L>.txt`` inside its (slide, level)."""
     dropout, mc_samples = mil_dropout.check_p(dropout), int(mc_samples)
     if mc_samples < 0 or mc_samples > mil_dropout.MC_MAX_SAMPLES:
         raise ValueError(f"mc_samples must be in 0..{mil_dropout.MC_MAX_SAMPLES}, got {mc_samples}")
     if mc_samples > 0 and dropout == 0.0:
         raise ValueError("Monte-Carlo dropout needs a dropout probability: give --mil_dropout P with 0 < P < 1 "
                          "(with P = 0 every sample is the same forward)")
-    feats, order, offsets, names, _ = load_triple(features_path, labels_path, paths_path, by_slide)
+    multiscale = features_path is None
+    if multiscale:
+        model_lv = mil_levels.model_levels(torch.load(model_path, map_location="cpu", weights_only=True)) if pooling == "attention" else None
+        if model_lv is None:
+            raise ValueError(f"{model_path} is not a levels model: give the triple of one level")
+        if levels is not None and tuple(int(v) for v in levels) != model_lv:
+            raise ValueError(f"levels = {','.join(str(int(v)) for v in levels)}, but {model_path} was trained on levels "
+                             f"{','.join(map(str, model_lv))}")
+        if dropout > 0.0 or mc_samples > 0:
+            raise ValueError("Monte-Carlo dropout with a levels model is not implemented: the fused pass is single-scale")
+        feats, level_rows, order, offsets, names, _, starts = mil_levels.load_triples(model_lv, data_dir)
+    else:
+        feats, order, offsets, names, _ = load_triple(features_path, labels_path, paths_path, by_slide)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    sd = {k: v.to(dev, torch.float32).contiguous() for k, v in torch.load(model_path, map_location="cpu", weights_only=True).items()}
+    sd = {k: v.to(dev, torch.int64 if k == mil_levels.LEVELS_KEY else torch.float32).contiguous()
+          for k, v in torch.load(model_path, map_location="cpu", weights_only=True).items()}
+    if not multiscale and (levels is not None or mil_levels.LEVELS_KEY in sd):
+        raise ValueError(f"{model_path} is a levels model: it is scored over the triples of its own levels, not over one triple"
+                         if mil_levels.LEVELS_KEY in sd else f"levels given, but {model_path} is not a levels model")
     model_heads = mil_heads.model_dims(sd, pooling)[0]
     if heads is not None and mil_heads.check_heads(heads) != model_heads:
         raise ValueError(f"heads = {heads}, but {model_path} has {model_heads} attention head(s)")
@@ -453,7 +529,8 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
         raise ValueError(f"save_attention needs attention pooling: {pooling} pooling has no attention weights")
     feats_dev = torch.from_numpy(feats).to(dev)
     f, offs = _gathered(feats_dev, np.arange(len(names)), order, offsets)
-    logits, attn = _score(sd, pooling, f, offs, want_attn=True)
+    score_lv = {"level_of": _gathered_levels(level_rows, np.arange(len(names)), order, offsets)} if multiscale else {}
+    logits, attn = _score(sd, pooling, f, offs, want_attn=True, **score_lv)
     prob = torch.softmax(logits, dim=1)[:, 1].cpu().numpy()
     pred = logits.argmax(1).cpu().numpy()
     out = [(n, float(p), int(y)) for n, p, y in zip(names, prob, pred)]
@@ -463,7 +540,12 @@ def predict_mil(model_path, features_path, labels_path, paths_path, *, pooling: 
         for n, p, y in out:
             fh.write(f"{n},{p:.6f},{y}\n")
     print(f"[INFO] MIL: {len(out)} bags scored -> {os.path.join(out_dir, 'results', 'mil_predictions.csv')}")
-    if save_attention:
+    if save_attention and multiscale:
+        for level, table in zip(model_lv, mil_levels.attention_tables(attn.cpu().numpy(), order, starts)):
+            path = os.path.join(out_dir, "results", f"mil_attention_{level}.npy")
+            np.save(path, table)
+            print(f"[INFO] MIL: attention of level {level} over {table.shape[0]} patches -> {path}")
+    elif save_attention:
         table = np.empty((feats.shape[0], model_heads), np.float32)
         table[order] = attn.cpu().numpy()  # gathered row i is line order[i] of the paths file
         path = os.path.join(out_dir, "results", "mil_attention.npy")
