@@ -59,6 +59,10 @@ named levels, every level has its own attention branch and softmax, the pooled v
 then not read.  ``--predict_mil`` reads the levels from the saved model; ``--mil_save_attention`` writes one
 ``results/mil_attention_<L>.npy`` per level.
 
+``--validate`` is the reference's feature sanity check (src/main.py:1017-1070) on the device: a two-component PCA and a
+class-weighted logistic-regression probe (Newton's method) on ``patch_features_<L>.npy`` / ``patch_labels_<L>.npy`` of
+``--patch_level`` -> ``results/validate_<L>.json``; ``--validate_save_pca`` adds ``results/pca_<L>.npy``.  No t-SNE.
+
 Everything else outside the hot path (download, plots) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
 """
@@ -72,7 +76,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-OUT_OF_SCOPE = ("download", "remote", "prepare", "validation", "validate", "evaluate",
+OUT_OF_SCOPE = ("download", "remote", "prepare", "validation", "evaluate",
                 "balance_dataset", "count_tumor_patches", "patch_one_slide", "slide", "move_files",
                 "check_good_downloaded_files")
 
@@ -89,6 +93,9 @@ def build_parser() -> argparse.ArgumentParser:
                    choices=["balanced", "weighted_loss", "self_supervised"])
     p.add_argument("--run_evaluation", action="store_true",
                    help="CAMELYON16 FROC evaluation of the detection CSVs (src/main.py:1168-1225)")
+    p.add_argument("--validate", action="store_true",
+                   help="sanity check of the feature files of --patch_level in the working directory (src/main.py:1017-1070): "
+                        "PCA and a logistic-regression probe on the device -> results/validate_<L>.json (rank 0)")
     for name in OUT_OF_SCOPE:
         if name in ("patch_one_slide", "slide"):
             p.add_argument(f"--{name}", type=str, default=None, help="(reference flag; out of scope here)")
@@ -185,6 +192,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--stain_beta", type=float, default=0.15, help="macenko: smallest optical density of a tissue pixel (> 0 and <= 1)")
     p.add_argument("--stain_target", type=str, default=None, help="macenko: JSON with the HE and maxC to map to (written by --stain_save_fit)")
     p.add_argument("--stain_save_fit", action="store_true", help="macenko: also write models/first_model/stain/<case>.json (HE, maxC, n, status)")
+    p.add_argument("--validate_save_pca", action="store_true",
+                   help="--validate: also write results/pca_<L>.npy, float32 [N, 2], row i = the two PCA coordinates of line i of "
+                        "patch_paths_<L>.txt")
+    p.add_argument("--validate_C", type=float, default=1.0, help="--validate: inverse regularisation strength of the probe (> 0)")
+    p.add_argument("--validate_tol", type=float, default=1e-4, help="--validate: the probe stops at max |gradient| <= this")
     p.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)
     return p
 
@@ -645,6 +657,52 @@ def cmd_mil(args, train: bool):
     return 0
 
 
+def cmd_validate(args) -> int:
+    """--validate: the reference's validate_resnet_classifier (src/main.py:1017-1070) on the feature files of every level
+    of --patch_level; validate.py has the driver."""
+    import json
+
+    from . import validate
+    from .dist import rank_world
+
+    if rank_world()[0] != 0:  # not sharded: rank 0 does it
+        return 0
+    if not args.validate_C > 0 or not args.validate_tol > 0:
+        print("[ERROR] --validate_C and --validate_tol must be positive.")
+        return 2
+    rc = 0
+    for level in levels_of(args):
+        features_path = os.path.join(os.getcwd(), f"patch_features_{level}.npy")
+        labels_path = os.path.join(os.getcwd(), f"patch_labels_{level}.npy")
+        if not os.path.exists(features_path) or not os.path.exists(labels_path):
+            print("[ERROR] Features or labels not found. Please run feature extraction first.")
+            rc = 1
+            continue
+        features, labels = np.load(features_path), np.load(labels_path)
+        print(f"[INFO] Feature shape: {features.shape}")
+        print(f"[INFO] Labels shape: {labels.shape}")
+        try:
+            labels = validate.check_labels(labels)
+            if features.ndim != 2 or features.shape[0] != labels.shape[0] or features.shape[0] == 0:
+                raise ValueError(f"features {features.shape} and labels {labels.shape} do not agree")
+            if features.shape[1] % 4 or not 4 <= features.shape[1] <= 2048:
+                raise ValueError(f"feature dimension {features.shape[1]}: a multiple of 4 in 4..2048 is supported")
+        except ValueError as e:
+            print(f"[ERROR] --validate, level {level}: {e}.")
+            rc = 2
+            continue
+        print(f"[INFO] Label distribution (0=normal, 1=tumor): {np.bincount(labels)}")
+        res = validate.run(features, labels, seed=42 if args.seed is None else args.seed, C_reg=args.validate_C,
+                           tol=args.validate_tol)
+        doc = validate.report(res)
+        os.makedirs("results", exist_ok=True)
+        with open(os.path.join("results", f"validate_{level}.json"), "w") as f:
+            json.dump(doc, f, indent=2)
+        if args.validate_save_pca:
+            np.save(os.path.join("results", f"pca_{level}.npy"), res["projection"])
+    return rc
+
+
 def _seed_everything(seed: int):
     import random
 
@@ -734,6 +792,8 @@ def _dispatch(args) -> int:
         rc = cmd_mil(args, True) or rc
     if args.predict_mil:
         rc = cmd_mil(args, False) or rc
+    if args.validate:
+        rc = cmd_validate(args) or rc
     return rc
 
 
