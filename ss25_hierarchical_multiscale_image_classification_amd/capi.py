@@ -597,6 +597,47 @@ def patches_normalize(patches: torch.Tensor, out_format: str = "nchw_f32", out: 
 MIL_POOLING = {"attention": 0, "mean": 1, "max": 2}
 
 
+def mil_weight_ptr(sd: Dict[str, torch.Tensor], key: str, dev) -> int:
+    """The device address of MIL weight ``sd[key]``; HipacError unless it is there as a contiguous float32 tensor on ``dev``."""
+    if key not in sd:
+        raise HipacError(f"state_dict lacks {key}")
+    t = sd[key]
+    if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+        raise HipacError(f"MIL weight {key} must be a contiguous float32 tensor on {dev}")
+    return t.data_ptr()
+
+
+def check_bag_offsets(bag_offsets, n: int) -> Tuple[torch.Tensor, int]:
+    """``bag_offsets`` int[n_bags + 1] (CPU or device) over ``n`` rows, validated on the host -> (int64 CPU tensor, n_bags)."""
+    offs_host = torch.as_tensor(bag_offsets).detach().to("cpu", torch.int64)
+    if offs_host.dim() != 1 or offs_host.numel() < 2 or int(offs_host[0]) != 0 or int(offs_host[-1]) != n or \
+            bool((offs_host[1:] <= offs_host[:-1]).any()):
+        raise HipacError("bag_offsets must start at 0, end at n and increase strictly (no empty bags)")
+    return offs_host, offs_host.numel() - 1
+
+
+def _mil_head_forward(lib, fn_name: str, query_name: str, params, K: int, feats: torch.Tensor, offs_host: torch.Tensor, extra_args,
+                      attn_shape, pooled_cols: int, what: str):
+    """The workspace query, the allocations, the call and its check for ``hipac_mil_{heads,gated,levels}_forward``
+    (``fn_name`` / ``query_name`` on ``lib``).  ``params``: the entry point's parameter struct, ``K`` its head / level count;
+    ``extra_args`` go in after ``feats``; ``attn_shape`` / ``pooled_cols``: None / 0 when that output is not wanted; ``what``
+    names the model in the refusal.  -> (logits, attn or None, pooled or None)."""
+    n, n_bags, dev = int(feats.shape[0]), offs_host.numel() - 1, feats.device
+    need = getattr(lib, query_name)(C.addressof(params), K, n, n_bags)
+    if need == 0:
+        raise HipacError(f"{what} MIL forward of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
+    offs = offs_host.to(torch.int32).to(dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    logits = torch.empty((n_bags, getattr(params, "base", params).num_classes), dtype=torch.float32, device=dev)
+    attn = None if attn_shape is None else torch.empty(attn_shape, dtype=torch.float32, device=dev)
+    pooled = torch.empty((n_bags, pooled_cols), dtype=torch.float32, device=dev) if pooled_cols else None
+    with torch.cuda.device(dev):
+        rc = getattr(lib, fn_name)(C.addressof(params), K, feats.data_ptr(), *extra_args, offs.data_ptr(), n, n_bags, logits.data_ptr(),
+                                   _ptr(attn), _ptr(pooled), ws.data_ptr(), ws.numel(), _stream())
+    _check(rc, fn_name)
+    return logits, attn, pooled
+
+
 def mil_forward(sd: Dict[str, torch.Tensor], pooling: str, feats: torch.Tensor, bag_offsets: torch.Tensor,
                 want_attn: bool = True, want_pooled: bool = False):
     """Score many bags at once.  ``sd``: MILClassifier state_dict tensors (float32, on the device of
@@ -607,31 +648,21 @@ def mil_forward(sd: Dict[str, torch.Tensor], pooling: str, feats: torch.Tensor, 
     _require_gpu(feats)
     if feats.dtype != torch.float32 or feats.dim() != 2:
         raise HipacError("feats must be float32[n, feature_dim]")
-    offs_host = bag_offsets.detach().to("cpu", torch.int64)
     n, F = int(feats.shape[0]), int(feats.shape[1])
-    if offs_host.dim() != 1 or offs_host.numel() < 2 or int(offs_host[0]) != 0 or int(offs_host[-1]) != n or \
-            bool((offs_host[1:] <= offs_host[:-1]).any()):
-        raise HipacError("bag_offsets must start at 0, end at n and increase strictly (no empty bags)")
-    n_bags = offs_host.numel() - 1
+    offs_host, n_bags = check_bag_offsets(bag_offsets, n)
     dev = feats.device
     offs = offs_host.to(torch.int32).to(dev)
-
-    def w(key):
-        t = sd[key]
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise HipacError(f"MIL weight {key} must be a contiguous float32 tensor on {dev}")
-        return t
-
+    w = lambda key: mil_weight_ptr(sd, key, dev)
     p = MilParams()
     attention = pooling == "attention"
     if attention:
-        p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight").data_ptr(), w("aggregator.attn_V.bias").data_ptr()
-        p.attn_U_w, p.attn_U_b = w("aggregator.attn_U.weight").data_ptr(), w("aggregator.attn_U.bias").data_ptr()
+        p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight"), w("aggregator.attn_V.bias")
+        p.attn_U_w, p.attn_U_b = w("aggregator.attn_U.weight"), w("aggregator.attn_U.bias")
         p.attn_dim = int(sd["aggregator.attn_V.weight"].shape[0])
         if tuple(sd["aggregator.attn_V.weight"].shape) != (p.attn_dim, F):
             raise HipacError("aggregator.attn_V.weight does not match feature_dim")
-    p.fc1_w, p.fc1_b = w("classifier.0.weight").data_ptr(), w("classifier.0.bias").data_ptr()
-    p.fc2_w, p.fc2_b = w("classifier.2.weight").data_ptr(), w("classifier.2.bias").data_ptr()
+    p.fc1_w, p.fc1_b = w("classifier.0.weight"), w("classifier.0.bias")
+    p.fc2_w, p.fc2_b = w("classifier.2.weight"), w("classifier.2.bias")
     p.feature_dim, p.hidden_dim = F, int(sd["classifier.0.weight"].shape[0])
     p.num_classes = int(sd["classifier.2.weight"].shape[0])
     if tuple(sd["classifier.0.weight"].shape) != (p.hidden_dim, F):

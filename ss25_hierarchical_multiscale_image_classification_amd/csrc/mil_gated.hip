@@ -15,11 +15,15 @@
 //
 // The tiling and the segment scheme are mil_train.hip's: 64 rows per tile whatever the bag boundaries, segment (tile t,
 // bag b) = id t + b, partial slabs added in a fixed order; no float atomics.  What does not depend on the gate comes
-// through mil_train_internal.h (row -> bag map, mil_heads.hip's pooling partials, pool combine, M . g, slab sums); the
-// per-head softmax has the form of mil_heads.hip's kernel but divides by the sum (see mg_softmax_kernel).
+// through mil_train_internal.h (row -> bag map, mil_heads.hip's pooling partials, pool combine, M . g, slab sums, and the
+// host side: the workspace plan with two hidden planes, the argument checks, the classifier chain) and mil_device.h (the
+// reductions, the K row dot products and the part2 write-out, shared with mil_heads.hip's kernels); the per-head softmax
+// has the form of mil_heads.hip's kernel but divides by the sum (see mg_softmax_kernel).  Here: the kernels whose
+// arithmetic has the gate in it, the forward up to the pooled vectors and the two entry points.
 #include "common.h"
 
 #include "../../include/hipac_mil_gated.h"
+#include "mil_device.h"
 #include "mil_train_internal.h"
 
 namespace hipac {
@@ -27,51 +31,8 @@ namespace hipac {
 constexpr int kMgTile = 64;  // rows per tile: mil_train.hip's kMtTile (mil_train_launch_pool_combine assumes it)
 constexpr int kMgMaxHeads = 8;
 
-struct MilGatedPlan {
-  int A_pad, ntiles, nseg, chunk, slices;
-  // floats of one tile's column sums: sum dT_i [A_pad] | sum dG_i [A_pad] | sum ds[i][k] (T_i o G_i) [K][A] | sum ds[i][k] [K]
-  size_t P2;
-  size_t bag_of, pooled, hid, dhid, dym, dlogits, g, ce, cdot, part, scores, attn, T, G, part2, slab, total;
-};
-
 static bool mil_gated_dims_ok(const hipac_mil_gated_params_t* p, int heads, int n, int n_bags) {
   return p && heads >= 1 && heads <= kMgMaxHeads && mil_train_sizes_ok(&p->base, n, n_bags);
-}
-
-static MilGatedPlan make_mil_gated_plan(const hipac_mil_params_t* p, int heads, int n, int n_bags, bool train) {
-  MilGatedPlan q{};
-  const size_t F = p->feature_dim, A = p->attn_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags, K = heads;
-  q.A_pad = (p->attn_dim + 31) / 32 * 32;
-  q.ntiles = (n + kMgTile - 1) / kMgTile;
-  q.nseg = q.ntiles + n_bags;
-  q.P2 = 2 * (size_t)q.A_pad + K * A + K;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align256(bytes);
-    return at;
-  };
-  q.bag_of = take((size_t)n * 4);
-  q.pooled = take(B * K * F * 4);
-  q.hid = take(B * Hd * 4);
-  q.part = take((size_t)q.nseg * K * F * 4);
-  q.scores = take((size_t)n * K * 4);
-  q.attn = take((size_t)n * K * 4);
-  q.T = take((size_t)n * q.A_pad * 4);
-  q.G = take((size_t)n * q.A_pad * 4);
-  if (train) {
-    mil_train_dv_slices(n, p->feature_dim, &q.chunk, &q.slices);
-    q.dhid = take(B * Hd * 4);
-    q.dym = take(B * Hd * 4);
-    q.dlogits = take(B * Cn * 4);
-    q.g = take(B * K * F * 4);
-    q.ce = take((2 + 8 * ((B + 255) / 256)) * 4);
-    q.cdot = take(B * K * 4);
-    q.part2 = take((size_t)q.ntiles * q.P2 * 4);
-    q.slab = take((size_t)q.slices * 2 * A * F * 4);  // per slice: dV [A][F] | dG_w [A][F]
-  }
-  q.total = o;
-  return q;
 }
 
 // T[m][j] = tanh(x_m . V[j] + b_V[j]) and G[m][j] = sigmoid(x_m . G_w[j] + b_G[j]) on v_mfma_f32_32x32x2_f32, in the form of
@@ -151,10 +112,7 @@ __global__ __launch_bounds__(256) void mg_score_kernel(const float* __restrict__
                                                        float* __restrict__ scores) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float u[K][4];
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) u[k][q] = lane + 64 * q < A ? Uw[k * A + lane + 64 * q] : 0.f;
+  mil_load_u<K>(Uw, A, lane, u);
   for (int rr = wave; rr < 16; rr += 4) {
     const int i = blockIdx.x * 16 + rr;
     if (i >= n) break;
@@ -169,24 +127,10 @@ __global__ __launch_bounds__(256) void mg_score_kernel(const float* __restrict__
       float v = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) v = fmaf(u[k][q], h[q], v);
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      v = mil_wave_sum(v);
       if (lane == 0) scores[(size_t)i * K + k] = v + Ub[k];
     }
   }
-}
-
-__device__ __forceinline__ float mg_block_reduce(float v, bool is_max, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float t = __shfl_down(v, o, 64);
-    v = is_max ? fmaxf(v, t) : v + t;
-  }
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < 4; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
 }
 
 // softmax of column k of the scores inside bag b: one workgroup per (bag, head) (mh_softmax_kernel's form).  The weight is
@@ -199,10 +143,10 @@ __global__ __launch_bounds__(256) void mg_softmax_kernel(const float* __restrict
   const int o0 = offs[b], o1 = offs[b + 1];
   float mx = -INFINITY;
   for (int i = o0 + tid; i < o1; i += 256) mx = fmaxf(mx, scores[(size_t)i * K + k]);
-  const float m = mg_block_reduce(mx, true, red);
+  const float m = mil_block_reduce(mx, true, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256) z += expf(scores[(size_t)i * K + k] - m);
-  const float zs = mg_block_reduce(z, false, red);
+  const float zs = mil_block_reduce(z, false, red);
   for (int i = o0 + tid; i < o1; i += 256) attn[(size_t)i * K + k] = expf(scores[(size_t)i * K + k] - m) / zs;
 }
 
@@ -220,11 +164,12 @@ __global__ __launch_bounds__(256) void mg_ds_kernel(const float* __restrict__ fe
   __shared__ float red[4][RED];
   const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float accT[4] = {0.f, 0.f, 0.f, 0.f}, accG[4] = {0.f, 0.f, 0.f, 0.f}, accU[K][4], accB[K], u[K][4];
+  mil_load_u<K>(Uw, A, lane, u);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     accB[k] = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) accU[k][q] = 0.f, u[k][q] = lane + 64 * q < A ? Uw[k * A + lane + 64 * q] : 0.f;
+    for (int q = 0; q < 4; ++q) accU[k][q] = 0.f;
   }
   const int F4 = F / 4;
   for (int rr = wave; rr < kMgTile; rr += 4) {
@@ -233,7 +178,9 @@ __global__ __launch_bounds__(256) void mg_ds_kernel(const float* __restrict__ fe
     const int b = bag_of[i];
     const f32x4* x = reinterpret_cast<const f32x4*>(feats + (size_t)(rows ? rows[i] : i) * F);
     const f32x4* gb = reinterpret_cast<const f32x4*>(g + (size_t)b * K * F);
-    float t[K];
+    // the K dot products: the same loop as in mil_heads.hip's mh_ds_kernel (as a function of mil_device.h it moved mh_ds_kernel's
+    // register counts, so it is written out in both)
+    float t[K], ds[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) t[k] = 0.f;
     for (int c = lane; c < F4; c += 64) {
@@ -245,12 +192,9 @@ __global__ __launch_bounds__(256) void mg_ds_kernel(const float* __restrict__ fe
         t[k] = fmaf(xv[3], gv[3], t[k]);
       }
     }
-    float ds[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      float v = t[k];
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      ds[k] = attn[(size_t)i * K + k] * (v - cdot[b * K + k]);
+      ds[k] = attn[(size_t)i * K + k] * (mil_wave_sum(t[k]) - cdot[b * K + k]);
       accB[k] += ds[k];
     }
 #pragma unroll
@@ -284,18 +228,7 @@ __global__ __launch_bounds__(256) void mg_ds_kernel(const float* __restrict__ fe
     for (int k = 0; k < K; ++k) red[wave][256 * (K + 2) + k] = accB[k];
   }
   __syncthreads();
-  float* out = part2 + (size_t)tile * (2 * (size_t)A_pad + (size_t)K * A + K);
-  for (int e = tid; e < RED; e += 256) {
-    const float s = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-    const int blk = e >> 8, j = e & 255;
-    if (blk < 2) {
-      if (j < A_pad) out[blk * A_pad + j] = s;
-    } else if (blk < K + 2) {
-      if (j < A) out[2 * A_pad + (blk - 2) * A + j] = s;
-    } else {
-      out[2 * A_pad + K * A + j] = s;
-    }
-  }
+  mil_store_part2<K, 2>(red, A, A_pad, tid, part2 + (size_t)tile * (2 * (size_t)A_pad + (size_t)K * A + K));
 }
 
 // dV and dG_w partials in one sweep of X, in the form of mt_dv_kernel: slab[slice][0][a][f] = sum over the slice's rows of
@@ -398,37 +331,24 @@ __global__ __launch_bounds__(256) void mg_dv_kernel(const float* __restrict__ dT
     }
 }
 
-#define MG_FOR_HEADS(heads, CALL) \
-  switch (heads) {                \
-    case 1: CALL(1); break;       \
-    case 2: CALL(2); break;       \
-    case 3: CALL(3); break;       \
-    case 4: CALL(4); break;       \
-    case 5: CALL(5); break;       \
-    case 6: CALL(6); break;       \
-    case 7: CALL(7); break;       \
-    default: CALL(8); break;      \
-  }
-
 // the forward up to the pooled vectors, shared by inference and the step: bag_of, T, G, a [n][K], pooled [n_bags][K F]
 static void mil_gated_pool(const hipac_mil_gated_params_t* gp, int K, const float* feats, const int32_t* rows,
-                           const int32_t* bag_offsets, int n, int n_bags, const MilGatedPlan& q, char* ws, float* a, float* pooled,
+                           const int32_t* bag_offsets, int n, int n_bags, const MilHeadPlan& q, char* ws, float* a, float* pooled,
                            hipStream_t s) {
   const hipac_mil_params_t* p = &gp->base;
   const int F = p->feature_dim, A = p->attn_dim;
   int32_t* bag_of = (int32_t*)(ws + q.bag_of);
-  float* T = (float*)(ws + q.T);
+  float* T = (float*)(ws + q.H);
   float* G = (float*)(ws + q.G);
   float* scores = (float*)(ws + q.scores);
   float* part = (float*)(ws + q.part);
   mil_train_launch_bag_of(bag_offsets, n_bags, n, bag_of, s);
   hipLaunchKernelGGL(mg_h_kernel, dim3(q.ntiles, (A + 63) / 64), dim3(256), 0, s, feats, rows, n, F, p->attn_V_w, p->attn_V_b,
                      gp->attn_G_w, gp->attn_G_b, A, q.A_pad, T, G);
-#define MG_SCORE(KK)                                                                                                          \
-  hipLaunchKernelGGL(mg_score_kernel<KK>, dim3((n + 15) / 16), dim3(256), 0, s, (const float*)T, (const float*)G, n, A, q.A_pad, \
-                     p->attn_U_w, p->attn_U_b, scores)
-  MG_FOR_HEADS(K, MG_SCORE)
-#undef MG_SCORE
+  mil_for_count<kMgMaxHeads>(K, [&](auto kk) {
+    hipLaunchKernelGGL(mg_score_kernel<decltype(kk)::value>, dim3((n + 15) / 16), dim3(256), 0, s, (const float*)T, (const float*)G, n,
+                       A, q.A_pad, p->attn_U_w, p->attn_U_b, scores);
+  });
   hipLaunchKernelGGL(mg_softmax_kernel, dim3(n_bags, K), dim3(256), 0, s, (const float*)scores, bag_offsets, K, a);
   mil_heads_launch_pool(feats, rows, bag_of, a, n, F, K, q.ntiles, part, s);
   mil_train_launch_pool_combine(part, bag_offsets, n_bags, K * F, pooled, s);
@@ -457,77 +377,52 @@ extern "C" {
 int hipac_mil_gated_abi_version(void) { return HIPAC_MIL_GATED_ABI_VERSION; }
 
 size_t hipac_mil_gated_forward_workspace_bytes(const hipac_mil_gated_params_t* params, int heads, int n, int n_bags) {
-  return mil_gated_dims_ok(params, heads, n, n_bags) ? make_mil_gated_plan(&params->base, heads, n, n_bags, false).total : 0;
+  return mil_gated_dims_ok(params, heads, n, n_bags) ? make_mil_head_plan(&params->base, heads, n, n_bags, 2, heads, false).total : 0;
 }
 
 size_t hipac_mil_gated_train_workspace_bytes(const hipac_mil_gated_params_t* params, int heads, int n, int n_bags) {
-  return mil_gated_dims_ok(params, heads, n, n_bags) ? make_mil_gated_plan(&params->base, heads, n, n_bags, true).total : 0;
+  return mil_gated_dims_ok(params, heads, n, n_bags) ? make_mil_head_plan(&params->base, heads, n, n_bags, 2, heads, true).total : 0;
 }
 
 int hipac_mil_gated_forward(const hipac_mil_gated_params_t* gp, int heads, const float* feats, const int32_t* bag_offsets, int n,
                             int n_bags, float* logits, float* attn, float* pooled, void* workspace, size_t workspace_bytes,
                             void* stream) {
-  HIPAC_REQUIRE(gp && feats && bag_offsets && logits && workspace, HIPAC_EINVAL, "mil_gated_forward: null argument");
-  const hipac_mil_params_t* p = &gp->base;
-  HIPAC_REQUIRE(heads >= 1 && heads <= kMgMaxHeads, HIPAC_EINVAL, "mil_gated_forward: heads %d (1..%d)", heads, kMgMaxHeads);
-  HIPAC_REQUIRE(mil_gated_dims_ok(gp, heads, n, n_bags), HIPAC_EINVAL,
-                "mil_gated_forward: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", n, n_bags,
-                p->feature_dim, p->attn_dim, p->hidden_dim, p->num_classes);
-  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b, HIPAC_EINVAL, "mil_gated_forward: classifier weights missing");
-  HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b && gp->attn_G_w && gp->attn_G_b, HIPAC_EINVAL,
-                "mil_gated_forward: attention weights missing");
-  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
-                "mil_gated_forward: feats / workspace must be 16-byte aligned");
-  const MilGatedPlan q = make_mil_gated_plan(p, heads, n, n_bags, false);
+  const hipac_mil_params_t* p = gp ? &gp->base : nullptr;
+  const int rc = mil_check_forward_args("mil_gated_forward", gp && feats && bag_offsets && logits && workspace, "heads", heads,
+                                        kMgMaxHeads, p, gp && gp->attn_G_w && gp->attn_G_b, n, n_bags, feats, workspace);
+  if (rc) return rc;
+  const MilHeadPlan q = make_mil_head_plan(p, heads, n, n_bags, 2, heads, false);
   HIPAC_REQUIRE(workspace_bytes >= q.total, HIPAC_EWORKSPACE, "mil_gated_forward: workspace %zu bytes, %zu needed", workspace_bytes,
                 q.total);
-  hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   float* a = attn ? attn : (float*)(ws + q.attn);
   float* pl = pooled ? pooled : (float*)(ws + q.pooled);
-  float* hid = (float*)(ws + q.hid);
-  mil_gated_pool(gp, heads, feats, nullptr, bag_offsets, n, n_bags, q, ws, a, pl, s);
+  mil_gated_pool(gp, heads, feats, nullptr, bag_offsets, n, n_bags, q, ws, a, pl, (hipStream_t)stream);
   HIPAC_CHECK_HIP(hipGetLastError());
-  int rc = hipac_linear_forward(pl, p->fc1_w, p->fc1_b, hid, n_bags, p->hidden_dim, heads * p->feature_dim, 1, stream);
-  if (rc) return rc;
-  return hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, n_bags, p->num_classes, p->hidden_dim, 0, stream);
+  return mil_classifier_forward(p, pl, heads * p->feature_dim, n_bags, (float*)(ws + q.hid), logits, stream);
 }
 
 int hipac_mil_gated_train_fwd_bwd(const hipac_mil_gated_params_t* gp, int heads, const float* feats, int n_feat_rows,
                                   const int32_t* rows, const int32_t* bag_offsets, int n, int n_bags, const int64_t* labels,
                                   const float* class_w, const hipac_mil_gated_params_t* ggrads, float* loss, float* logits,
                                   float* attn, void* workspace, size_t workspace_bytes, int accumulate, void* stream) {
-  HIPAC_REQUIRE(gp && feats && bag_offsets && labels && ggrads && loss && logits && workspace, HIPAC_EINVAL,
-                "mil_gated_train_fwd_bwd: null argument");
-  const hipac_mil_params_t* p = &gp->base;
-  const hipac_mil_params_t* grads = &ggrads->base;
-  HIPAC_REQUIRE(heads >= 1 && heads <= kMgMaxHeads, HIPAC_EINVAL, "mil_gated_train_fwd_bwd: heads %d (1..%d)", heads, kMgMaxHeads);
-  HIPAC_REQUIRE(mil_gated_dims_ok(gp, heads, n, n_bags), HIPAC_EINVAL,
-                "mil_gated_train_fwd_bwd: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", n, n_bags,
-                p->feature_dim, p->attn_dim, p->hidden_dim, p->num_classes);
-  HIPAC_REQUIRE(n_feat_rows > 0 && (rows || n <= n_feat_rows), HIPAC_EINVAL, "mil_gated_train_fwd_bwd: n_feat_rows %d for n %d rows",
-                n_feat_rows, n);
-  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b && grads->fc1_w && grads->fc1_b && grads->fc2_w && grads->fc2_b,
-                HIPAC_EINVAL, "mil_gated_train_fwd_bwd: classifier weights or their gradient buffers missing");
-  HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b && gp->attn_G_w && gp->attn_G_b && grads->attn_V_w &&
-                    grads->attn_V_b && grads->attn_U_w && grads->attn_U_b && ggrads->attn_G_w && ggrads->attn_G_b,
-                HIPAC_EINVAL, "mil_gated_train_fwd_bwd: attention weights or their gradient buffers missing");
-  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
-                "mil_gated_train_fwd_bwd: feats / workspace must be 16-byte aligned");
-  const MilGatedPlan q = make_mil_gated_plan(p, heads, n, n_bags, true);
+  const bool ptrs = gp && feats && bag_offsets && labels && ggrads && loss && logits && workspace;
+  const hipac_mil_params_t* p = ptrs ? &gp->base : nullptr;
+  const hipac_mil_params_t* grads = ptrs ? &ggrads->base : nullptr;
+  int rc = mil_check_train_args("mil_gated_train_fwd_bwd", ptrs, "heads", heads, kMgMaxHeads, p, grads, true,
+                                ptrs && gp->attn_G_w && gp->attn_G_b && ggrads->attn_G_w && ggrads->attn_G_b, n, n_bags, n_feat_rows,
+                                rows != nullptr, feats, workspace);
+  if (rc) return rc;
+  const MilHeadPlan q = make_mil_head_plan(p, heads, n, n_bags, 2, heads, true);
   HIPAC_REQUIRE(workspace_bytes >= q.total, HIPAC_EWORKSPACE, "mil_gated_train_fwd_bwd: workspace %zu bytes, %zu needed",
                 workspace_bytes, q.total);
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  const int F = p->feature_dim, A = p->attn_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags, K = heads;
+  const int F = p->feature_dim, A = p->attn_dim, B = n_bags, K = heads;
   float* pooled = (float*)(ws + q.pooled);
-  float* hid = (float*)(ws + q.hid);
-  float* dhid = (float*)(ws + q.dhid);
-  float* dym = (float*)(ws + q.dym);
-  float* dlogits = (float*)(ws + q.dlogits);
   float* g = (float*)(ws + q.g);
   float* a = attn ? attn : (float*)(ws + q.attn);
-  float* T = (float*)(ws + q.T);
+  float* T = (float*)(ws + q.H);
   float* G = (float*)(ws + q.G);
   float* cdot = (float*)(ws + q.cdot);
   float* part2 = (float*)(ws + q.part2);
@@ -535,26 +430,16 @@ int hipac_mil_gated_train_fwd_bwd(const hipac_mil_gated_params_t* gp, int heads,
 
   mil_gated_pool(gp, K, feats, rows, bag_offsets, n, B, q, ws, a, pooled, s);
   HIPAC_CHECK_HIP(hipGetLastError());
-  // classifier.0 over the K F pooled columns + ReLU, classifier.2, cross-entropy, and their backward: hipac.h's entry points
-  int rc = hipac_linear_forward(pooled, p->fc1_w, p->fc1_b, hid, B, Hd, K * F, 1, stream);
-  if (rc) return rc;
-  rc = hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, B, Cn, Hd, 0, stream);
-  if (rc) return rc;
-  rc = hipac_cross_entropy_fwd_bwd(logits, labels, class_w, B, Cn, loss, dlogits, (float*)(ws + q.ce), stream);
-  if (rc) return rc;
-  rc = hipac_linear_backward(hid, p->fc2_w, dlogits, nullptr, nullptr, dhid, (float*)grads->fc2_w, (float*)grads->fc2_b, B, Cn, Hd,
-                             accumulate, stream);
-  if (rc) return rc;
-  rc = hipac_linear_backward(pooled, p->fc1_w, dhid, hid, dym, g, (float*)grads->fc1_w, (float*)grads->fc1_b, B, Hd, K * F,
-                             accumulate, stream);
+  // classifier.0 over the K F pooled columns + ReLU, classifier.2, cross-entropy, and their backward
+  rc = mil_classifier_fwd_bwd(p, grads, K * F, B, labels, class_w, loss, logits, q, ws, true, accumulate, stream, nullptr, nullptr);
   if (rc) return rc;
   // pooled and g are [B K][F]: cdot[b][k] = M[b][k] . g[b][k]
   mil_train_launch_cdot(pooled, g, F, B * K, cdot, s);
-#define MG_DS(KK)                                                                                                               \
-  hipLaunchKernelGGL(mg_ds_kernel<KK>, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)(ws + q.bag_of), (const float*)a, \
-                     (const float*)g, (const float*)cdot, p->attn_U_w, T, G, n, F, A, q.A_pad, part2)
-  MG_FOR_HEADS(K, MG_DS)
-#undef MG_DS
+  mil_for_count<kMgMaxHeads>(K, [&](auto kk) {
+    hipLaunchKernelGGL(mg_ds_kernel<decltype(kk)::value>, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)(ws + q.bag_of),
+                       (const float*)a, (const float*)g, (const float*)cdot, p->attn_U_w, T, G, n, F, A, q.A_pad, part2);
+  });
+  // two hidden planes in part2 and two products per slice in slab: the end of the step is not mil_head_launch_grads'
   const size_t Ap = (size_t)q.A_pad;
   mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 0, A, (float*)grads->attn_V_b, accumulate, s);
   mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, Ap, A, (float*)ggrads->attn_G_b, accumulate, s);

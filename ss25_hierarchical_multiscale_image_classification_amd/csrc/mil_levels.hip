@@ -11,7 +11,10 @@
 // but a row belongs to ONE level, so its score, its pooling FMA, its row dot product and its ds U product are formed once here
 // where a masked L-head step forms them L times to produce zeros.  X V^T, dV = dH^T X, the row -> bag map, the per-bag
 // combination of the pooling segments (over L F columns), the M . g products (over B L rows) and the fixed-order slab sums are
-// mil_train.hip's, launched through mil_train_internal.h as mil_heads.hip launches them.  The tiling and the segment scheme are
+// mil_train.hip's, launched through mil_train_internal.h as mil_heads.hip launches them; the workspace plan (with scores and
+// attn one column wide), the argument checks, the classifier chain and the end of the step (db_V | dU | db_U | dV) are that
+// header's as well, the reductions inside the kernels mil_device.h's.  Here: the ml_ kernels, the forward up to the pooled
+// vectors and the two entry points.  The tiling and the segment scheme are
 // mil_train.hip's: 64 rows per tile whatever the bag boundaries, segment (tile t, bag b) = id t + b; no float atomics.
 // The level of a row is uniform over the wave (pooling: over the workgroup) that handles it, so the per-level accumulators are
 // picked by a uniform switch over registers, never by a dynamic index.  A level_of value >= L is a row of no level: it is
@@ -19,6 +22,7 @@
 #include "common.h"
 
 #include "../../include/hipac_mil_levels.h"
+#include "mil_device.h"
 #include "mil_train_internal.h"
 
 namespace hipac {
@@ -26,49 +30,8 @@ namespace hipac {
 constexpr int kMlTile = 64;  // rows per tile: mil_train.hip's kMtTile (mil_train_launch_pool_combine assumes it)
 constexpr int kMlMaxLevels = HIPAC_MIL_MAX_LEVELS;
 
-struct MilLevelsPlan {
-  int A_pad, ntiles, nseg, chunk, slices;
-  size_t P2;  // floats of one tile's column sums: sum dH_i [A_pad] | sum ds_i H_i routed into [L][A] | sum ds_i routed into [L]
-  size_t bag_of, pooled, hid, dhid, dym, dlogits, g, ce, cdot, part, scores, attn, H, part2, slab, total;
-};
-
 static bool mil_levels_dims_ok(const hipac_mil_params_t* p, int levels, int n, int n_bags) {
   return levels >= 1 && levels <= kMlMaxLevels && mil_train_sizes_ok(p, n, n_bags);
-}
-
-static MilLevelsPlan make_mil_levels_plan(const hipac_mil_params_t* p, int levels, int n, int n_bags, bool train) {
-  MilLevelsPlan q{};
-  const size_t F = p->feature_dim, A = p->attn_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags, L = levels;
-  q.A_pad = (p->attn_dim + 31) / 32 * 32;
-  q.ntiles = (n + kMlTile - 1) / kMlTile;
-  q.nseg = q.ntiles + n_bags;
-  q.P2 = (size_t)q.A_pad + L * A + L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align256(bytes);
-    return at;
-  };
-  q.bag_of = take((size_t)n * 4);
-  q.pooled = take(B * L * F * 4);
-  q.hid = take(B * Hd * 4);
-  q.part = take((size_t)q.nseg * L * F * 4);
-  q.scores = take((size_t)n * 4);
-  q.attn = take((size_t)n * 4);
-  q.H = take((size_t)n * q.A_pad * 4);
-  if (train) {
-    mil_train_dv_slices(n, p->feature_dim, &q.chunk, &q.slices);
-    q.dhid = take(B * Hd * 4);
-    q.dym = take(B * Hd * 4);
-    q.dlogits = take(B * Cn * 4);
-    q.g = take(B * L * F * 4);
-    q.ce = take((2 + 8 * ((B + 255) / 256)) * 4);
-    q.cdot = take(B * L * 4);
-    q.part2 = take((size_t)q.ntiles * q.P2 * 4);
-    q.slab = take((size_t)q.slices * A * F * 4);
-  }
-  q.total = o;
-  return q;
 }
 
 // s_i = U[lev(i)] . H_i + b_U[lev(i)]: one wave per row, 16 rows per workgroup, one dot product per row.  U is L A floats and
@@ -91,23 +54,9 @@ __global__ __launch_bounds__(256) void ml_score_kernel(const float* __restrict__
       const int j = lane + 64 * q;
       if (j < A) v = fmaf(Uw[lev * A + j], H[(size_t)i * A_pad + j], v);
     }
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = mil_wave_sum(v);
     if (lane == 0) scores[i] = v + Ub[lev];
   }
-}
-
-__device__ __forceinline__ float ml_block_reduce(float v, bool is_max, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float t = __shfl_down(v, o, 64);
-    v = is_max ? fmaxf(v, t) : v + t;
-  }
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < 4; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
 }
 
 // softmax over the rows of level k inside bag b: one workgroup per (bag, level), the rows taken in row order.  An empty
@@ -124,11 +73,11 @@ __global__ __launch_bounds__(256) void ml_softmax_kernel(const float* __restrict
     if (lev == k) mx = fmaxf(mx, scores[i]);
     if (k == 0 && lev >= L) attn[i] = 0.f;
   }
-  const float m = ml_block_reduce(mx, true, red);
+  const float m = mil_block_reduce(mx, true, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256)
     if (level_of[i] == k) z += expf(scores[i] - m);
-  z = ml_block_reduce(z, false, red);
+  z = mil_block_reduce(z, false, red);
   if (!(z > 0.f)) return;  // the same z in every thread
   const float inv = 1.f / z;
   for (int i = o0 + tid; i < o1; i += 256)
@@ -256,8 +205,7 @@ __global__ __launch_bounds__(256) void ml_ds_kernel(const float* __restrict__ fe
       const f32x4 xv = x[c], gv = gb[c];
       t = fmaf(xv[0], gv[0], t), t = fmaf(xv[1], gv[1], t), t = fmaf(xv[2], gv[2], t), t = fmaf(xv[3], gv[3], t);
     }
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    const float ds = attn[i] * (t - cdot[b * L + lev]);
+    const float ds = attn[i] * (mil_wave_sum(t) - cdot[b * L + lev]);
     switch (lev) {
       case 0: ml_ds_row<L, 0>(ds, u, accU, accB, accV, hrow, lane, A, A_pad); break;
       case 1: ml_ds_row<L, 1>(ds, u, accU, accB, accV, hrow, lane, A, A_pad); break;
@@ -276,31 +224,12 @@ __global__ __launch_bounds__(256) void ml_ds_kernel(const float* __restrict__ fe
     for (int k = 0; k < L; ++k) red[wave][256 * (L + 1) + k] = accB[k];
   }
   __syncthreads();
-  float* out = part2 + (size_t)tile * ((size_t)A_pad + (size_t)L * A + L);
-  for (int e = tid; e < RED; e += 256) {
-    const float s = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-    const int blk = e >> 8, j = e & 255;
-    if (blk == 0) {
-      if (j < A_pad) out[j] = s;
-    } else if (blk <= L) {
-      if (j < A) out[A_pad + (blk - 1) * A + j] = s;
-    } else {
-      out[A_pad + L * A + j] = s;
-    }
-  }
+  mil_store_part2<L, 1>(red, A, A_pad, tid, part2 + (size_t)tile * ((size_t)A_pad + (size_t)L * A + L));
 }
-
-#define ML_FOR_LEVELS(levels, CALL) \
-  switch (levels) {                 \
-    case 1: CALL(1); break;         \
-    case 2: CALL(2); break;         \
-    case 3: CALL(3); break;         \
-    default: CALL(4); break;        \
-  }
 
 // the forward up to the pooled vectors, shared by inference and the step: bag_of, H, a [n], pooled [n_bags][L F]
 static void mil_levels_pool(const hipac_mil_params_t* p, int L, const float* feats, const int32_t* rows, const uint8_t* level_of,
-                            const int32_t* bag_offsets, int n, int n_bags, const MilLevelsPlan& q, char* ws, float* a, float* pooled,
+                            const int32_t* bag_offsets, int n, int n_bags, const MilHeadPlan& q, char* ws, float* a, float* pooled,
                             hipStream_t s) {
   const int F = p->feature_dim, A = p->attn_dim;
   int32_t* bag_of = (int32_t*)(ws + q.bag_of);
@@ -312,11 +241,10 @@ static void mil_levels_pool(const hipac_mil_params_t* p, int L, const float* fea
   hipLaunchKernelGGL(ml_score_kernel, dim3((n + 15) / 16), dim3(256), 0, s, (const float*)H, level_of, n, A, q.A_pad, L, p->attn_U_w,
                      p->attn_U_b, scores);
   hipLaunchKernelGGL(ml_softmax_kernel, dim3(n_bags, L), dim3(256), 0, s, (const float*)scores, level_of, bag_offsets, L, a);
-#define ML_POOL(LL)                                                                                                                 \
-  hipLaunchKernelGGL(ml_pool_kernel<LL>, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)bag_of, level_of, (const float*)a, \
-                     n, F, part)
-  ML_FOR_LEVELS(L, ML_POOL)
-#undef ML_POOL
+  mil_for_count<kMlMaxLevels>(L, [&](auto ll) {
+    hipLaunchKernelGGL(ml_pool_kernel<decltype(ll)::value>, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)bag_of,
+                       level_of, (const float*)a, n, F, part);
+  });
   mil_train_launch_pool_combine(part, bag_offsets, n_bags, L * F, pooled, s);
 }
 
@@ -329,106 +257,62 @@ extern "C" {
 int hipac_mil_levels_abi_version(void) { return HIPAC_MIL_LEVELS_ABI_VERSION; }
 
 size_t hipac_mil_levels_forward_workspace_bytes(const hipac_mil_params_t* params, int levels, int n, int n_bags) {
-  return mil_levels_dims_ok(params, levels, n, n_bags) ? make_mil_levels_plan(params, levels, n, n_bags, false).total : 0;
+  return mil_levels_dims_ok(params, levels, n, n_bags) ? make_mil_head_plan(params, levels, n, n_bags, 1, 1, false).total : 0;
 }
 
 size_t hipac_mil_levels_train_workspace_bytes(const hipac_mil_params_t* params, int levels, int n, int n_bags) {
-  return mil_levels_dims_ok(params, levels, n, n_bags) ? make_mil_levels_plan(params, levels, n, n_bags, true).total : 0;
+  return mil_levels_dims_ok(params, levels, n, n_bags) ? make_mil_head_plan(params, levels, n, n_bags, 1, 1, true).total : 0;
 }
 
 int hipac_mil_levels_forward(const hipac_mil_params_t* p, int levels, const float* feats, const uint8_t* level_of,
                              const int32_t* bag_offsets, int n, int n_bags, float* logits, float* attn, float* pooled, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  HIPAC_REQUIRE(p && feats && level_of && bag_offsets && logits && workspace, HIPAC_EINVAL, "mil_levels_forward: null argument");
-  HIPAC_REQUIRE(levels >= 1 && levels <= kMlMaxLevels, HIPAC_EINVAL, "mil_levels_forward: levels %d (1..%d)", levels, kMlMaxLevels);
-  HIPAC_REQUIRE(mil_levels_dims_ok(p, levels, n, n_bags), HIPAC_EINVAL,
-                "mil_levels_forward: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", n, n_bags,
-                p->feature_dim, p->attn_dim, p->hidden_dim, p->num_classes);
-  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b, HIPAC_EINVAL, "mil_levels_forward: classifier weights missing");
-  HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b, HIPAC_EINVAL, "mil_levels_forward: attention weights missing");
-  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
-                "mil_levels_forward: feats / workspace must be 16-byte aligned");
-  const MilLevelsPlan q = make_mil_levels_plan(p, levels, n, n_bags, false);
+  const int rc = mil_check_forward_args("mil_levels_forward", p && feats && level_of && bag_offsets && logits && workspace, "levels",
+                                        levels, kMlMaxLevels, p, true, n, n_bags, feats, workspace);
+  if (rc) return rc;
+  const MilHeadPlan q = make_mil_head_plan(p, levels, n, n_bags, 1, 1, false);
   HIPAC_REQUIRE(workspace_bytes >= q.total, HIPAC_EWORKSPACE, "mil_levels_forward: workspace %zu bytes, %zu needed", workspace_bytes,
                 q.total);
-  hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   float* a = attn ? attn : (float*)(ws + q.attn);
   float* pl = pooled ? pooled : (float*)(ws + q.pooled);
-  float* hid = (float*)(ws + q.hid);
-  mil_levels_pool(p, levels, feats, nullptr, level_of, bag_offsets, n, n_bags, q, ws, a, pl, s);
+  mil_levels_pool(p, levels, feats, nullptr, level_of, bag_offsets, n, n_bags, q, ws, a, pl, (hipStream_t)stream);
   HIPAC_CHECK_HIP(hipGetLastError());
-  int rc = hipac_linear_forward(pl, p->fc1_w, p->fc1_b, hid, n_bags, p->hidden_dim, levels * p->feature_dim, 1, stream);
-  if (rc) return rc;
-  return hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, n_bags, p->num_classes, p->hidden_dim, 0, stream);
+  return mil_classifier_forward(p, pl, levels * p->feature_dim, n_bags, (float*)(ws + q.hid), logits, stream);
 }
 
 int hipac_mil_levels_train_fwd_bwd(const hipac_mil_params_t* p, int levels, const float* feats, int n_feat_rows, const int32_t* rows,
                                    const uint8_t* level_of, const int32_t* bag_offsets, int n, int n_bags, const int64_t* labels,
                                    const float* class_w, const hipac_mil_params_t* grads, float* loss, float* logits, float* attn,
                                    void* workspace, size_t workspace_bytes, int accumulate, void* stream) {
-  HIPAC_REQUIRE(p && feats && level_of && bag_offsets && labels && grads && loss && logits && workspace, HIPAC_EINVAL,
-                "mil_levels_train_fwd_bwd: null argument");
-  HIPAC_REQUIRE(levels >= 1 && levels <= kMlMaxLevels, HIPAC_EINVAL, "mil_levels_train_fwd_bwd: levels %d (1..%d)", levels,
-                kMlMaxLevels);
-  HIPAC_REQUIRE(mil_levels_dims_ok(p, levels, n, n_bags), HIPAC_EINVAL,
-                "mil_levels_train_fwd_bwd: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", n, n_bags,
-                p->feature_dim, p->attn_dim, p->hidden_dim, p->num_classes);
-  HIPAC_REQUIRE(n_feat_rows > 0 && (rows || n <= n_feat_rows), HIPAC_EINVAL, "mil_levels_train_fwd_bwd: n_feat_rows %d for n %d rows",
-                n_feat_rows, n);
-  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b && grads->fc1_w && grads->fc1_b && grads->fc2_w && grads->fc2_b,
-                HIPAC_EINVAL, "mil_levels_train_fwd_bwd: classifier weights or their gradient buffers missing");
-  HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b && grads->attn_V_w && grads->attn_V_b && grads->attn_U_w &&
-                    grads->attn_U_b,
-                HIPAC_EINVAL, "mil_levels_train_fwd_bwd: attention weights or their gradient buffers missing");
-  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
-                "mil_levels_train_fwd_bwd: feats / workspace must be 16-byte aligned");
-  const MilLevelsPlan q = make_mil_levels_plan(p, levels, n, n_bags, true);
+  int rc = mil_check_train_args("mil_levels_train_fwd_bwd",
+                                p && feats && level_of && bag_offsets && labels && grads && loss && logits && workspace, "levels", levels,
+                                kMlMaxLevels, p, grads, true, true, n, n_bags, n_feat_rows, rows != nullptr, feats, workspace);
+  if (rc) return rc;
+  const MilHeadPlan q = make_mil_head_plan(p, levels, n, n_bags, 1, 1, true);
   HIPAC_REQUIRE(workspace_bytes >= q.total, HIPAC_EWORKSPACE, "mil_levels_train_fwd_bwd: workspace %zu bytes, %zu needed",
                 workspace_bytes, q.total);
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  const int F = p->feature_dim, A = p->attn_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags, L = levels;
+  const int F = p->feature_dim, A = p->attn_dim, B = n_bags, L = levels;
   float* pooled = (float*)(ws + q.pooled);
-  float* hid = (float*)(ws + q.hid);
-  float* dhid = (float*)(ws + q.dhid);
-  float* dym = (float*)(ws + q.dym);
-  float* dlogits = (float*)(ws + q.dlogits);
   float* g = (float*)(ws + q.g);
   float* a = attn ? attn : (float*)(ws + q.attn);
-  float* H = (float*)(ws + q.H);
   float* cdot = (float*)(ws + q.cdot);
-  float* part2 = (float*)(ws + q.part2);
-  float* slab = (float*)(ws + q.slab);
 
   mil_levels_pool(p, L, feats, rows, level_of, bag_offsets, n, B, q, ws, a, pooled, s);
   HIPAC_CHECK_HIP(hipGetLastError());
-  // classifier.0 over the L F pooled columns + ReLU, classifier.2, cross-entropy, and their backward: hipac.h's entry points
-  int rc = hipac_linear_forward(pooled, p->fc1_w, p->fc1_b, hid, B, Hd, L * F, 1, stream);
-  if (rc) return rc;
-  rc = hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, B, Cn, Hd, 0, stream);
-  if (rc) return rc;
-  rc = hipac_cross_entropy_fwd_bwd(logits, labels, class_w, B, Cn, loss, dlogits, (float*)(ws + q.ce), stream);
-  if (rc) return rc;
-  rc = hipac_linear_backward(hid, p->fc2_w, dlogits, nullptr, nullptr, dhid, (float*)grads->fc2_w, (float*)grads->fc2_b, B, Cn, Hd,
-                             accumulate, stream);
-  if (rc) return rc;
-  rc = hipac_linear_backward(pooled, p->fc1_w, dhid, hid, dym, g, (float*)grads->fc1_w, (float*)grads->fc1_b, B, Hd, L * F, accumulate,
-                             stream);
+  // classifier.0 over the L F pooled columns + ReLU, classifier.2, cross-entropy, and their backward
+  rc = mil_classifier_fwd_bwd(p, grads, L * F, B, labels, class_w, loss, logits, q, ws, true, accumulate, stream, nullptr, nullptr);
   if (rc) return rc;
   // pooled and g are [B L][F]: cdot[b][k] = M[b][k] . g[b][k]
   mil_train_launch_cdot(pooled, g, F, B * L, cdot, s);
-#define ML_DS(LL)                                                                                                                \
-  hipLaunchKernelGGL(ml_ds_kernel<LL>, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)(ws + q.bag_of), level_of,        \
-                     (const float*)a, (const float*)g, (const float*)cdot, p->attn_U_w, H, n, F, A, q.A_pad, part2)
-  ML_FOR_LEVELS(L, ML_DS)
-#undef ML_DS
-  mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 0, A, (float*)grads->attn_V_b, accumulate, s);
-  mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, (size_t)q.A_pad, (long long)L * A, (float*)grads->attn_U_w, accumulate, s);
-  mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, (size_t)q.A_pad + (size_t)L * A, L, (float*)grads->attn_U_b, accumulate, s);
-  mil_train_launch_dv(H, feats, rows, n, F, A, q.A_pad, q.chunk, q.slices, slab, s);
-  const long long total = (long long)A * F;
-  mil_train_launch_slab_reduce(slab, q.slices, (size_t)total, 0, total, (float*)grads->attn_V_w, accumulate, s);
+  mil_for_count<kMlMaxLevels>(L, [&](auto ll) {
+    hipLaunchKernelGGL(ml_ds_kernel<decltype(ll)::value>, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)(ws + q.bag_of),
+                       level_of, (const float*)a, (const float*)g, (const float*)cdot, p->attn_U_w, (float*)(ws + q.H), n, F, A, q.A_pad,
+                       (float*)(ws + q.part2));
+  });
+  mil_head_launch_grads(grads, L, feats, rows, n, F, A, q, ws, accumulate, s);
   HIPAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

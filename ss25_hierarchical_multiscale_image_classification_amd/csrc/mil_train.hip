@@ -17,20 +17,18 @@
 // mean / max pooling have no parameter in front of the classifier: the features are data, not parameters, so their
 // backward ends at dL/dpooled.
 // The classifier, the cross-entropy and Adam are hipac.h's hipac_linear_* / hipac_cross_entropy_fwd_bwd / hipac_adam_step.
+// This file also defines what mil_train_internal.h declares for the K-head steps (mil_heads.hip, mil_gated.hip,
+// mil_levels.hip): their workspace plan, argument checks, classifier chain and the launches that do not depend on K.
 #include "common.h"
 
 #include "../../include/hipac_mil_train.h"
+#include "mil_device.h"
 #include "mil_train_internal.h"
 
 namespace hipac {
 
 constexpr int kMtTile = 64;         // rows per tile (pooling, ds sweep)
 constexpr int kMtMaxRows = 1 << 24;  // n * A_pad stays far inside size_t and the tile counts inside int
-
-struct MilTrainPlan {
-  int A_pad, ntiles, nseg, chunk, slices;
-  size_t bag_of, pooled, hid, dhid, dym, dlogits, g, ce, cdot, part, scores, attn, H, part2, slab, total;
-};
 
 static bool mil_train_dims_ok(const hipac_mil_params_t* p, int pooling, int n, int n_bags) {
   if (!p || pooling < HIPAC_MIL_ATTENTION || pooling > HIPAC_MIL_MAX) return false;
@@ -41,8 +39,9 @@ static bool mil_train_dims_ok(const hipac_mil_params_t* p, int pooling, int n, i
   return true;
 }
 
-static MilTrainPlan make_mil_train_plan(const hipac_mil_params_t* p, int pooling, int n, int n_bags) {
-  MilTrainPlan q{};
+// the single-head step's layout of MilHeadPlan's buffers (no G; P2 = sum dH_i [A_pad] | sum ds_i H_i [A_pad] | sum ds_i)
+static MilHeadPlan make_mil_train_plan(const hipac_mil_params_t* p, int pooling, int n, int n_bags) {
+  MilHeadPlan q{};
   const size_t F = p->feature_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags;
   const bool att = pooling == HIPAC_MIL_ATTENTION;
   q.A_pad = att ? (p->attn_dim + 31) / 32 * 32 : 0;
@@ -69,7 +68,8 @@ static MilTrainPlan make_mil_train_plan(const hipac_mil_params_t* p, int pooling
     q.scores = take((size_t)n * 4);
     q.attn = take((size_t)n * 4);
     q.H = take((size_t)n * q.A_pad * 4);
-    q.part2 = take((size_t)q.ntiles * (2 * q.A_pad + 1) * 4);
+    q.P2 = 2 * (size_t)q.A_pad + 1;
+    q.part2 = take((size_t)q.ntiles * q.P2 * 4);
     q.slab = take((size_t)q.slices * p->attn_dim * F * 4);
   }
   q.total = o;
@@ -155,23 +155,9 @@ __global__ __launch_bounds__(256) void mt_score_kernel(const float* __restrict__
     if (i >= n) break;
     float v = 0.f;
     for (int j = lane; j < A; j += 64) v = fmaf(Uw[j], H[(size_t)i * A_pad + j], v);
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = mil_wave_sum(v);
     if (lane == 0) scores[i] = v + Ub[0];
   }
-}
-
-__device__ __forceinline__ float mt_block_reduce(float v, bool is_max, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float t = __shfl_down(v, o, 64);
-    v = is_max ? fmaxf(v, t) : v + t;
-  }
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < 4; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
 }
 
 // softmax of the scores inside each bag.  4 bytes per row: the one per-bag pass of the step; everything that touches
@@ -183,10 +169,10 @@ __global__ __launch_bounds__(256) void mt_softmax_kernel(const float* __restrict
   const int o0 = offs[b], o1 = offs[b + 1];
   float mx = -INFINITY;
   for (int i = o0 + tid; i < o1; i += 256) mx = fmaxf(mx, scores[i]);
-  const float m = mt_block_reduce(mx, true, red);
+  const float m = mil_block_reduce(mx, true, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256) z += expf(scores[i] - m);
-  const float inv = 1.f / mt_block_reduce(z, false, red);
+  const float inv = 1.f / mil_block_reduce(z, false, red);
   for (int i = o0 + tid; i < o1; i += 256) attn[i] = expf(scores[i] - m) * inv;
 }
 
@@ -268,7 +254,7 @@ __global__ __launch_bounds__(256) void mt_cdot_kernel(const float* __restrict__ 
   if (b >= B) return;
   float v = 0.f;
   for (int f = lane; f < F; f += 64) v = fmaf(pooled[(size_t)b * F + f], g[(size_t)b * F + f], v);
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = mil_wave_sum(v);
   if (lane == 0) cdot[b] = v;
 }
 
@@ -297,8 +283,7 @@ __global__ __launch_bounds__(256) void mt_ds_kernel(const float* __restrict__ fe
       const f32x4 xv = x[c], gv = gb[c];
       t = fmaf(xv[0], gv[0], t), t = fmaf(xv[1], gv[1], t), t = fmaf(xv[2], gv[2], t), t = fmaf(xv[3], gv[3], t);
     }
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    const float ds = attn[i] * (t - cdot[b]);
+    const float ds = attn[i] * (mil_wave_sum(t) - cdot[b]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int j = lane + 64 * q;
@@ -445,6 +430,121 @@ __global__ __launch_bounds__(256) void mt_l2_add_kernel(float* __restrict__ g, c
 
 namespace hipac {
 
+// mil_train_internal.h: what the K-head steps share with this one on the host
+MilHeadPlan make_mil_head_plan(const hipac_mil_params_t* p, int K, int n, int n_bags, int planes, int attn_cols, bool train) {
+  MilHeadPlan q{};
+  const size_t F = p->feature_dim, A = p->attn_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags, Kh = K;
+  q.A_pad = (p->attn_dim + 31) / 32 * 32;
+  q.ntiles = (n + kMtTile - 1) / kMtTile;
+  q.nseg = q.ntiles + n_bags;
+  q.P2 = (size_t)planes * q.A_pad + Kh * A + Kh;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align256(bytes);
+    return at;
+  };
+  q.bag_of = take((size_t)n * 4);
+  q.pooled = take(B * Kh * F * 4);
+  q.hid = take(B * Hd * 4);
+  q.part = take((size_t)q.nseg * Kh * F * 4);
+  q.scores = take((size_t)n * attn_cols * 4);
+  q.attn = take((size_t)n * attn_cols * 4);
+  q.H = take((size_t)n * q.A_pad * 4);
+  if (planes == 2) q.G = take((size_t)n * q.A_pad * 4);
+  if (train) {
+    mil_train_dv_slices(n, p->feature_dim, &q.chunk, &q.slices);
+    q.dhid = take(B * Hd * 4);
+    q.dym = take(B * Hd * 4);
+    q.dlogits = take(B * Cn * 4);
+    q.g = take(B * Kh * F * 4);
+    q.ce = take((2 + 8 * ((B + 255) / 256)) * 4);
+    q.cdot = take(B * Kh * 4);
+    q.part2 = take((size_t)q.ntiles * q.P2 * 4);
+    q.slab = take((size_t)q.slices * planes * A * F * 4);
+  }
+  q.total = o;
+  return q;
+}
+
+int mil_check_forward_args(const char* who, bool ptrs, const char* count_name, int count, int max_count, const hipac_mil_params_t* p,
+                           bool gate, int n, int n_bags, const void* feats, const void* workspace) {
+  HIPAC_REQUIRE(ptrs, HIPAC_EINVAL, "%s: null argument", who);
+  HIPAC_REQUIRE(count >= 1 && count <= max_count, HIPAC_EINVAL, "%s: %s %d (1..%d)", who, count_name, count, max_count);
+  HIPAC_REQUIRE(mil_train_sizes_ok(p, n, n_bags), HIPAC_EINVAL,
+                "%s: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", who, n, n_bags, p->feature_dim,
+                p->attn_dim, p->hidden_dim, p->num_classes);
+  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b, HIPAC_EINVAL, "%s: classifier weights missing", who);
+  HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b && gate, HIPAC_EINVAL, "%s: attention weights missing", who);
+  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
+                "%s: feats / workspace must be 16-byte aligned", who);
+  return 0;
+}
+
+int mil_check_train_args(const char* who, bool ptrs, const char* count_name, int count, int max_count, const hipac_mil_params_t* p,
+                         const hipac_mil_params_t* grads, bool attention, bool gate, int n, int n_bags, int n_feat_rows, bool has_rows,
+                         const void* feats, const void* workspace) {
+  HIPAC_REQUIRE(ptrs, HIPAC_EINVAL, "%s: null argument", who);
+  if (count_name)
+    HIPAC_REQUIRE(count >= 1 && count <= max_count, HIPAC_EINVAL, "%s: %s %d (1..%d)", who, count_name, count, max_count);
+  HIPAC_REQUIRE(mil_train_dims_ok(p, attention ? HIPAC_MIL_ATTENTION : HIPAC_MIL_MEAN, n, n_bags), HIPAC_EINVAL,
+                "%s: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", who, n, n_bags, p->feature_dim,
+                p->attn_dim, p->hidden_dim, p->num_classes);
+  HIPAC_REQUIRE(n_feat_rows > 0 && (has_rows || n <= n_feat_rows), HIPAC_EINVAL, "%s: n_feat_rows %d for n %d rows", who, n_feat_rows, n);
+  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b && grads->fc1_w && grads->fc1_b && grads->fc2_w && grads->fc2_b,
+                HIPAC_EINVAL, "%s: classifier weights or their gradient buffers missing", who);
+  if (attention)
+    HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b && grads->attn_V_w && grads->attn_V_b &&
+                      grads->attn_U_w && grads->attn_U_b && gate,
+                  HIPAC_EINVAL, "%s: attention weights or their gradient buffers missing", who);
+  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
+                "%s: feats / workspace must be 16-byte aligned", who);
+  return 0;
+}
+
+int mil_classifier_forward(const hipac_mil_params_t* p, const float* pooled, int cols, int B, float* hid, float* logits, void* stream) {
+  const int rc = hipac_linear_forward(pooled, p->fc1_w, p->fc1_b, hid, B, p->hidden_dim, cols, 1, stream);
+  if (rc) return rc;
+  return hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, B, p->num_classes, p->hidden_dim, 0, stream);
+}
+
+int mil_classifier_fwd_bwd(const hipac_mil_params_t* p, const hipac_mil_params_t* grads, int cols, int B, const int64_t* labels,
+                           const float* class_w, float* loss, float* logits, const MilHeadPlan& q, char* ws, bool want_g, int accumulate,
+                           void* stream, MilHiddenHook hook, void* hook_ctx) {
+  const int Hd = p->hidden_dim, Cn = p->num_classes;
+  hipStream_t s = (hipStream_t)stream;
+  float* pooled = (float*)(ws + q.pooled);
+  float* hid = (float*)(ws + q.hid);
+  float* dhid = (float*)(ws + q.dhid);
+  float* dlogits = (float*)(ws + q.dlogits);
+  int rc = hipac_linear_forward(pooled, p->fc1_w, p->fc1_b, hid, B, Hd, cols, 1, stream);
+  if (rc) return rc;
+  if (hook && (rc = hook(hid, B, Hd, hook_ctx, s))) return rc;
+  rc = hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, B, Cn, Hd, 0, stream);
+  if (rc) return rc;
+  rc = hipac_cross_entropy_fwd_bwd(logits, labels, class_w, B, Cn, loss, dlogits, (float*)(ws + q.ce), stream);
+  if (rc) return rc;
+  rc = hipac_linear_backward(hid, p->fc2_w, dlogits, nullptr, nullptr, dhid, (float*)grads->fc2_w, (float*)grads->fc2_b, B, Cn, Hd,
+                             accumulate, stream);
+  if (rc) return rc;
+  if (hook && (rc = hook(dhid, B, Hd, hook_ctx, s))) return rc;
+  return hipac_linear_backward(pooled, p->fc1_w, dhid, hid, (float*)(ws + q.dym), want_g ? (float*)(ws + q.g) : nullptr,
+                               (float*)grads->fc1_w, (float*)grads->fc1_b, B, Hd, cols, accumulate, stream);
+}
+
+void mil_head_launch_grads(const hipac_mil_params_t* grads, int K, const float* feats, const int32_t* rows, int n, int F, int A,
+                           const MilHeadPlan& q, char* ws, int accumulate, hipStream_t s) {
+  const float* part2 = (const float*)(ws + q.part2);
+  float* slab = (float*)(ws + q.slab);
+  const size_t Ap = (size_t)q.A_pad;
+  mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 0, A, (float*)grads->attn_V_b, accumulate, s);
+  mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, Ap, (long long)K * A, (float*)grads->attn_U_w, accumulate, s);
+  mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, Ap + (size_t)K * A, K, (float*)grads->attn_U_b, accumulate, s);
+  mil_train_launch_dv((const float*)(ws + q.H), feats, rows, n, F, A, q.A_pad, q.chunk, q.slices, slab, s);
+  const long long total = (long long)A * F;
+  mil_train_launch_slab_reduce(slab, q.slices, (size_t)total, 0, total, (float*)grads->attn_V_w, accumulate, s);
+}
+
 // The step itself.  `hook` (mil_train_internal.h) is called on hid after classifier.0 + ReLU and on dhid after
 // classifier.2's backward; hipac_mil_train_fwd_bwd passes none.
 int mil_train_run(const hipac_mil_params_t* p, int pooling, const float* feats, int n_feat_rows, const int32_t* rows,
@@ -454,32 +554,18 @@ int mil_train_run(const hipac_mil_params_t* p, int pooling, const float* feats, 
   HIPAC_REQUIRE(p && feats && bag_offsets && labels && grads && loss && logits && workspace, HIPAC_EINVAL,
                 "mil_train_fwd_bwd: null argument");
   HIPAC_REQUIRE(pooling >= HIPAC_MIL_ATTENTION && pooling <= HIPAC_MIL_MAX, HIPAC_EINVAL, "mil_train_fwd_bwd: pooling %d", pooling);
-  HIPAC_REQUIRE(mil_train_dims_ok(p, pooling, n, n_bags), HIPAC_EINVAL,
-                "mil_train_fwd_bwd: n %d, n_bags %d, feature_dim %d, attn_dim %d, hidden_dim %d, num_classes %d", n, n_bags,
-                p->feature_dim, p->attn_dim, p->hidden_dim, p->num_classes);
-  HIPAC_REQUIRE(n_feat_rows > 0 && (rows || n <= n_feat_rows), HIPAC_EINVAL, "mil_train_fwd_bwd: n_feat_rows %d for n %d rows",
-                n_feat_rows, n);
-  HIPAC_REQUIRE(p->fc1_w && p->fc1_b && p->fc2_w && p->fc2_b && grads->fc1_w && grads->fc1_b && grads->fc2_w && grads->fc2_b,
-                HIPAC_EINVAL, "mil_train_fwd_bwd: classifier weights or their gradient buffers missing");
   const bool att = pooling == HIPAC_MIL_ATTENTION;
-  if (att)
-    HIPAC_REQUIRE(p->attn_V_w && p->attn_V_b && p->attn_U_w && p->attn_U_b && grads->attn_V_w && grads->attn_V_b &&
-                      grads->attn_U_w && grads->attn_U_b,
-                  HIPAC_EINVAL, "mil_train_fwd_bwd: attention weights or their gradient buffers missing");
-  HIPAC_REQUIRE(((uintptr_t)feats & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HIPAC_EINVAL,
-                "mil_train_fwd_bwd: feats / workspace must be 16-byte aligned");
-  const MilTrainPlan q = make_mil_train_plan(p, pooling, n, n_bags);
+  int rc = mil_check_train_args("mil_train_fwd_bwd", true, nullptr, 0, 0, p, grads, att, true, n, n_bags, n_feat_rows, rows != nullptr,
+                                feats, workspace);
+  if (rc) return rc;
+  const MilHeadPlan q = make_mil_train_plan(p, pooling, n, n_bags);
   HIPAC_REQUIRE(workspace_bytes >= q.total, HIPAC_EWORKSPACE, "mil_train_fwd_bwd: workspace %zu bytes, %zu needed", workspace_bytes,
                 q.total);
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  const int F = p->feature_dim, A = p->attn_dim, Hd = p->hidden_dim, Cn = p->num_classes, B = n_bags;
+  const int F = p->feature_dim, A = p->attn_dim, B = n_bags;
   int32_t* bag_of = (int32_t*)(ws + q.bag_of);
   float* pooled = (float*)(ws + q.pooled);
-  float* hid = (float*)(ws + q.hid);
-  float* dhid = (float*)(ws + q.dhid);
-  float* dym = (float*)(ws + q.dym);
-  float* dlogits = (float*)(ws + q.dlogits);
   float* g = (float*)(ws + q.g);
   float* part = (float*)(ws + q.part);
   float* a = att ? (attn ? attn : (float*)(ws + q.attn)) : nullptr;
@@ -498,47 +584,28 @@ int mil_train_run(const hipac_mil_params_t* p, int pooling, const float* feats, 
   hipLaunchKernelGGL(mt_pool_combine_kernel, dim3(B, (F + 31) / 32), dim3(256), 0, s, (const float*)part, bag_offsets, F, pooling,
                      pooled);
   HIPAC_CHECK_HIP(hipGetLastError());
-  // classifier.0 + ReLU, classifier.2, cross-entropy, and their backward: hipac.h's entry points as they are
-  int rc = hipac_linear_forward(pooled, p->fc1_w, p->fc1_b, hid, B, Hd, F, 1, stream);
-  if (rc) return rc;
-  if (hook && (rc = hook(hid, B, Hd, hook_ctx, s))) return rc;
-  rc = hipac_linear_forward(hid, p->fc2_w, p->fc2_b, logits, B, Cn, Hd, 0, stream);
-  if (rc) return rc;
-  rc = hipac_cross_entropy_fwd_bwd(logits, labels, class_w, B, Cn, loss, dlogits, (float*)(ws + q.ce), stream);
-  if (rc) return rc;
-  rc = hipac_linear_backward(hid, p->fc2_w, dlogits, nullptr, nullptr, dhid, (float*)grads->fc2_w, (float*)grads->fc2_b, B, Cn, Hd,
-                             accumulate, stream);
-  if (rc) return rc;
-  if (hook && (rc = hook(dhid, B, Hd, hook_ctx, s))) return rc;
-  rc = hipac_linear_backward(pooled, p->fc1_w, dhid, hid, dym, att ? g : nullptr, (float*)grads->fc1_w, (float*)grads->fc1_b, B, Hd,
-                             F, accumulate, stream);
+  rc = mil_classifier_fwd_bwd(p, grads, F, B, labels, class_w, loss, logits, q, ws, att, accumulate, stream, hook, hook_ctx);
   if (rc) return rc;
   if (att) {
     float* cdot = (float*)(ws + q.cdot);
     float* part2 = (float*)(ws + q.part2);
     float* slab = (float*)(ws + q.slab);
-    const size_t P2 = 2 * (size_t)q.A_pad + 1;
     hipLaunchKernelGGL(mt_cdot_kernel, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)pooled, (const float*)g, F, B, cdot);
     hipLaunchKernelGGL(mt_ds_kernel, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)bag_of, (const float*)a,
                        (const float*)g, (const float*)cdot, p->attn_U_w, H, n, F, A, q.A_pad, part2);
-    hipLaunchKernelGGL(mt_slab_reduce_kernel, dim3((A + 31) / 32), dim3(256), 0, s, (const float*)part2, q.ntiles, P2, (size_t)0,
-                       (long long)A, (float*)grads->attn_V_b, accumulate);
-    hipLaunchKernelGGL(mt_slab_reduce_kernel, dim3((A + 31) / 32), dim3(256), 0, s, (const float*)part2, q.ntiles, P2,
-                       (size_t)q.A_pad, (long long)A, (float*)grads->attn_U_w, accumulate);
-    hipLaunchKernelGGL(mt_slab_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)part2, q.ntiles, P2, 2 * (size_t)q.A_pad,
-                       1LL, (float*)grads->attn_U_b, accumulate);
-    hipLaunchKernelGGL(mt_dv_kernel, dim3((F + 63) / 64, q.slices), dim3(256), 0, s, (const float*)H, feats, rows, n, F, A, q.A_pad,
-                       q.chunk, slab);
+    mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 0, A, (float*)grads->attn_V_b, accumulate, s);
+    mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, (size_t)q.A_pad, A, (float*)grads->attn_U_w, accumulate, s);
+    mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 2 * (size_t)q.A_pad, 1, (float*)grads->attn_U_b, accumulate, s);
+    mil_train_launch_dv(H, feats, rows, n, F, A, q.A_pad, q.chunk, q.slices, slab, s);
     const long long total = (long long)A * F;
-    hipLaunchKernelGGL(mt_slab_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, s, (const float*)slab, q.slices,
-                       (size_t)total, (size_t)0, total, (float*)grads->attn_V_w, accumulate);
+    mil_train_launch_slab_reduce(slab, q.slices, (size_t)total, 0, total, (float*)grads->attn_V_w, accumulate, s);
     HIPAC_CHECK_HIP(hipGetLastError());
   }
   return 0;
 }
 
-// mil_train_internal.h: the launches of the kernels above that do not depend on the number of attention heads, for
-// mil_heads.hip.  The same launch shapes as in mil_train_run.
+// mil_train_internal.h: the launches of the kernels above that do not depend on the number of attention heads.  The same
+// launch shapes as in mil_train_run.
 bool mil_train_sizes_ok(const hipac_mil_params_t* p, int n, int n_bags) { return mil_train_dims_ok(p, HIPAC_MIL_ATTENTION, n, n_bags); }
 
 // dV: one workgroup = 64 feature columns x all of A x one slice of rows; about 512 workgroups in all

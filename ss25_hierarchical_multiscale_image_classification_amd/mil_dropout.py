@@ -124,24 +124,16 @@ def dropout_mask(p: float, seed: int, sample: int, site: int, n_rows: int, n_col
 
 def mil_params(sd: Dict[str, torch.Tensor], pooling: str, F: int, dev) -> capi.MilParams:
     """hipac_mil_params_t over the tensors of a MILClassifier state_dict (contiguous float32 on ``dev``)."""
-
-    def w(key):
-        if key not in sd:
-            raise capi.HipacError(f"state_dict lacks {key}")
-        t = sd[key]
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise capi.HipacError(f"MIL weight {key} must be a contiguous float32 tensor on {dev}")
-        return t
-
+    w = lambda key: capi.mil_weight_ptr(sd, key, dev)
     p = capi.MilParams()
     if pooling == "attention":
-        p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight").data_ptr(), w("aggregator.attn_V.bias").data_ptr()
-        p.attn_U_w, p.attn_U_b = w("aggregator.attn_U.weight").data_ptr(), w("aggregator.attn_U.bias").data_ptr()
+        p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight"), w("aggregator.attn_V.bias")
+        p.attn_U_w, p.attn_U_b = w("aggregator.attn_U.weight"), w("aggregator.attn_U.bias")
         p.attn_dim = int(sd["aggregator.attn_V.weight"].shape[0])
         if tuple(sd["aggregator.attn_V.weight"].shape) != (p.attn_dim, F):
             raise capi.HipacError("aggregator.attn_V.weight does not match feature_dim")
-    p.fc1_w, p.fc1_b = w("classifier.0.weight").data_ptr(), w("classifier.0.bias").data_ptr()
-    p.fc2_w, p.fc2_b = w("classifier.2.weight").data_ptr(), w("classifier.2.bias").data_ptr()
+    p.fc1_w, p.fc1_b = w("classifier.0.weight"), w("classifier.0.bias")
+    p.fc2_w, p.fc2_b = w("classifier.2.weight"), w("classifier.2.bias")
     p.feature_dim, p.hidden_dim = F, int(sd["classifier.0.weight"].shape[0])
     p.num_classes = int(sd["classifier.2.weight"].shape[0])
     if tuple(sd["classifier.0.weight"].shape) != (p.hidden_dim, F):

@@ -98,13 +98,7 @@ def mil_gated_params(sd: Dict[str, torch.Tensor], dev) -> Tuple[MilGatedParams, 
     """(hipac_mil_gated_params_t over the tensors of a gated MILClassifier state_dict, heads); ValueError on a shape that does
     not agree (``gated_dims``), HipacError on a tensor that is not contiguous float32 on ``dev``."""
     K, F, A = gated_dims(sd)
-
-    def w(key):
-        t = sd[key]
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise capi.HipacError(f"MIL weight {key} must be a contiguous float32 tensor on {dev}")
-        return t.data_ptr()
-
+    w = lambda key: capi.mil_weight_ptr(sd, key, dev)
     g = MilGatedParams()
     p = g.base
     p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight"), w("aggregator.attn_V.bias")
@@ -129,24 +123,9 @@ def gated_forward(sd: Dict[str, torch.Tensor], feats: torch.Tensor, bag_offsets,
     capi._require_gpu(feats)
     if feats.dtype != torch.float32:
         raise capi.HipacError("feats must be float32[n, feature_dim]")
-    offs_host = torch.as_tensor(bag_offsets).detach().to("cpu", torch.int64)
     n = int(feats.shape[0])
-    if offs_host.dim() != 1 or offs_host.numel() < 2 or int(offs_host[0]) != 0 or int(offs_host[-1]) != n or \
-            bool((offs_host[1:] <= offs_host[:-1]).any()):
-        raise capi.HipacError("bag_offsets must start at 0, end at n and increase strictly (no empty bags)")
-    n_bags, dev = offs_host.numel() - 1, feats.device
+    offs_host, _ = capi.check_bag_offsets(bag_offsets, n)
     lib = load_mil_gated_library()
-    g, K = mil_gated_params(sd, dev)
-    need = lib.hipac_mil_gated_forward_workspace_bytes(C.addressof(g), K, n, n_bags)
-    if need == 0:
-        raise capi.HipacError(f"gated MIL forward of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
-    offs = offs_host.to(torch.int32).to(dev)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    logits = torch.empty((n_bags, g.base.num_classes), dtype=torch.float32, device=dev)
-    attn = torch.empty((n, K), dtype=torch.float32, device=dev) if want_attn else None
-    pooled = torch.empty((n_bags, K * F), dtype=torch.float32, device=dev) if want_pooled else None
-    with torch.cuda.device(dev):
-        rc = lib.hipac_mil_gated_forward(C.addressof(g), K, feats.data_ptr(), offs.data_ptr(), n, n_bags, logits.data_ptr(),
-                                         capi._ptr(attn), capi._ptr(pooled), ws.data_ptr(), ws.numel(), capi._stream())
-    capi._check(rc, "hipac_mil_gated_forward")
-    return logits, attn, pooled
+    g, K = mil_gated_params(sd, feats.device)
+    return capi._mil_head_forward(lib, "hipac_mil_gated_forward", "hipac_mil_gated_forward_workspace_bytes", g, K, feats, offs_host, (),
+                                  (n, K) if want_attn else None, K * F if want_pooled else 0, "gated")

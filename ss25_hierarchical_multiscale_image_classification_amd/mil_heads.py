@@ -81,20 +81,12 @@ def model_dims(sd: Dict[str, torch.Tensor], pooling: str) -> Tuple[int, int]:
 def mil_heads_params(sd: Dict[str, torch.Tensor], F: int, dev) -> Tuple[capi.MilParams, int]:
     """(hipac_mil_params_t over the tensors of a multi-head MILClassifier state_dict, heads); the tensors must be contiguous
     float32 on ``dev`` and agree in shape: attn_U [K][A], classifier.0 [hidden][K F]."""
-
-    def w(key):
-        if key not in sd:
-            raise capi.HipacError(f"state_dict lacks {key}")
-        t = sd[key]
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise capi.HipacError(f"MIL weight {key} must be a contiguous float32 tensor on {dev}")
-        return t
-
+    w = lambda key: capi.mil_weight_ptr(sd, key, dev)
     p = capi.MilParams()
-    p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight").data_ptr(), w("aggregator.attn_V.bias").data_ptr()
-    p.attn_U_w, p.attn_U_b = w("aggregator.attn_U.weight").data_ptr(), w("aggregator.attn_U.bias").data_ptr()
-    p.fc1_w, p.fc1_b = w("classifier.0.weight").data_ptr(), w("classifier.0.bias").data_ptr()
-    p.fc2_w, p.fc2_b = w("classifier.2.weight").data_ptr(), w("classifier.2.bias").data_ptr()
+    p.attn_V_w, p.attn_V_b = w("aggregator.attn_V.weight"), w("aggregator.attn_V.bias")
+    p.attn_U_w, p.attn_U_b = w("aggregator.attn_U.weight"), w("aggregator.attn_U.bias")
+    p.fc1_w, p.fc1_b = w("classifier.0.weight"), w("classifier.0.bias")
+    p.fc2_w, p.fc2_b = w("classifier.2.weight"), w("classifier.2.bias")
     A, K = int(sd["aggregator.attn_V.weight"].shape[0]), heads_of(sd)
     p.feature_dim, p.attn_dim, p.hidden_dim = F, A, int(sd["classifier.0.weight"].shape[0])
     p.num_classes = int(sd["classifier.2.weight"].shape[0])
@@ -119,24 +111,9 @@ def heads_forward(sd: Dict[str, torch.Tensor], feats: torch.Tensor, bag_offsets,
     capi._require_gpu(feats)
     if feats.dtype != torch.float32 or feats.dim() != 2:
         raise capi.HipacError("feats must be float32[n, feature_dim]")
-    offs_host = torch.as_tensor(bag_offsets).detach().to("cpu", torch.int64)
     n, F = int(feats.shape[0]), int(feats.shape[1])
-    if offs_host.dim() != 1 or offs_host.numel() < 2 or int(offs_host[0]) != 0 or int(offs_host[-1]) != n or \
-            bool((offs_host[1:] <= offs_host[:-1]).any()):
-        raise capi.HipacError("bag_offsets must start at 0, end at n and increase strictly (no empty bags)")
-    n_bags, dev = offs_host.numel() - 1, feats.device
+    offs_host, _ = capi.check_bag_offsets(bag_offsets, n)
     lib = load_mil_heads_library()
-    p, K = mil_heads_params(sd, F, dev)
-    need = lib.hipac_mil_heads_forward_workspace_bytes(C.addressof(p), K, n, n_bags)
-    if need == 0:
-        raise capi.HipacError(f"multi-head MIL forward of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
-    offs = offs_host.to(torch.int32).to(dev)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    logits = torch.empty((n_bags, p.num_classes), dtype=torch.float32, device=dev)
-    attn = torch.empty((n, K), dtype=torch.float32, device=dev) if want_attn else None
-    pooled = torch.empty((n_bags, K * F), dtype=torch.float32, device=dev) if want_pooled else None
-    with torch.cuda.device(dev):
-        rc = lib.hipac_mil_heads_forward(C.addressof(p), K, feats.data_ptr(), offs.data_ptr(), n, n_bags, logits.data_ptr(),
-                                         capi._ptr(attn), capi._ptr(pooled), ws.data_ptr(), ws.numel(), capi._stream())
-    capi._check(rc, "hipac_mil_heads_forward")
-    return logits, attn, pooled
+    p, K = mil_heads_params(sd, F, feats.device)
+    return capi._mil_head_forward(lib, "hipac_mil_heads_forward", "hipac_mil_heads_forward_workspace_bytes", p, K, feats, offs_host, (),
+                                  (n, K) if want_attn else None, K * F if want_pooled else 0, "multi-head")

@@ -144,32 +144,16 @@ def levels_forward(sd: Dict[str, torch.Tensor], feats: torch.Tensor, bag_offsets
     capi._require_gpu(feats)
     if feats.dtype != torch.float32 or feats.dim() != 2:
         raise capi.HipacError("feats must be float32[n, feature_dim]")
-    offs_host = torch.as_tensor(bag_offsets).detach().to("cpu", torch.int64)
     n, F = int(feats.shape[0]), int(feats.shape[1])
-    if offs_host.dim() != 1 or offs_host.numel() < 2 or int(offs_host[0]) != 0 or int(offs_host[-1]) != n or \
-            bool((offs_host[1:] <= offs_host[:-1]).any()):
-        raise capi.HipacError("bag_offsets must start at 0, end at n and increase strictly (no empty bags)")
+    offs_host, _ = capi.check_bag_offsets(bag_offsets, n)
     lv = _check_level_of(level_of, n)
-    n_bags, dev = offs_host.numel() - 1, feats.device
     lib = load_mil_levels_library()
-    p, L = mil_heads_params(sd, F, dev)  # the shapes of a model of L heads
+    p, L = mil_heads_params(sd, F, feats.device)  # the shapes of a model of L heads
     if L > MAX_LEVELS:
         raise capi.HipacError(f"aggregator.attn_U.weight has {L} rows: 1..{MAX_LEVELS} levels are supported")
-    need = lib.hipac_mil_levels_forward_workspace_bytes(C.addressof(p), L, n, n_bags)
-    if need == 0:
-        raise capi.HipacError(f"multiscale MIL forward of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
-    offs = offs_host.to(torch.int32).to(dev)
-    lv_dev = lv.to(dev, torch.uint8).contiguous()
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    logits = torch.empty((n_bags, p.num_classes), dtype=torch.float32, device=dev)
-    attn = torch.empty(n, dtype=torch.float32, device=dev) if want_attn else None
-    pooled = torch.empty((n_bags, L * F), dtype=torch.float32, device=dev) if want_pooled else None
-    with torch.cuda.device(dev):
-        rc = lib.hipac_mil_levels_forward(C.addressof(p), L, feats.data_ptr(), lv_dev.data_ptr(), offs.data_ptr(), n, n_bags,
-                                          logits.data_ptr(), capi._ptr(attn), capi._ptr(pooled), ws.data_ptr(), ws.numel(),
-                                          capi._stream())
-    capi._check(rc, "hipac_mil_levels_forward")
-    return logits, attn, pooled
+    lv_dev = lv.to(feats.device, torch.uint8).contiguous()
+    return capi._mil_head_forward(lib, "hipac_mil_levels_forward", "hipac_mil_levels_forward_workspace_bytes", p, L, feats, offs_host,
+                                  (lv_dev.data_ptr(),), n if want_attn else None, L * F if want_pooled else 0, "multiscale")
 
 
 # ----------------------------------------------------------------------------

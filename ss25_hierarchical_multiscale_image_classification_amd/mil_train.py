@@ -109,14 +109,23 @@ class NativeMILTrainer:
         if self.gated:
             mil_gated.gated_dims(sd)  # ValueError if the gate's shapes disagree with attn_V, before anything is loaded
         self.lib = load_mil_train_library()
-        if self.dropout > 0.0:
-            mil_dropout.load_mil_dropout_library()
+        # the step's entry point, decided once: (workspace query, step, the int after the params -- heads / levels / pooling --,
+        # the arguments that follow `accumulate`, whether attn is [n] and not [n, heads])
         if self.gated:
             mil_gated.load_mil_gated_library()
+            self._entry = ("hipac_mil_gated_train_workspace_bytes", "hipac_mil_gated_train_fwd_bwd", self.heads, lambda: (), False)
         elif self.levels is not None:
             mil_levels.load_mil_levels_library()
+            self._entry = ("hipac_mil_levels_train_workspace_bytes", "hipac_mil_levels_train_fwd_bwd", self.heads, lambda: (), True)
         elif self.heads > 1:
             mil_heads.load_mil_heads_library()
+            self._entry = ("hipac_mil_heads_train_workspace_bytes", "hipac_mil_heads_train_fwd_bwd", self.heads, lambda: (), False)
+        elif self.dropout > 0.0:
+            mil_dropout.load_mil_dropout_library()
+            self._entry = ("hipac_mil_dropout_train_workspace_bytes", "hipac_mil_dropout_train_fwd_bwd", capi.MIL_POOLING[pooling],
+                           lambda: (self.dropout, self.seed, self.steps & 0xFFFFFFFF), True)
+        else:
+            self._entry = ("hipac_mil_train_workspace_bytes", "hipac_mil_train_fwd_bwd", capi.MIL_POOLING[pooling], lambda: (), True)
         self.pooling, self.device, self.weight_decay = pooling, torch.device(device), float(weight_decay)
         if self.device.type != "cuda":
             raise capi.HipacError("NativeMILTrainer needs a ROCm device: there is no CPU fallback")
@@ -217,41 +226,23 @@ class NativeMILTrainer:
         lab = lab.to(self.device).contiguous()
         offs_dev = torch.from_numpy(offs.astype(np.int32)).to(self.device)
         lv_dev = None if level_of is None else mil_levels._check_level_of(level_of, n).to(self.device, torch.uint8).contiguous()
-        pool = capi.MIL_POOLING[self.pooling]
-        if self.levels is not None:  # `levels` takes the place of `pooling` in both calls
-            pool, query = self.heads, self.lib.hipac_mil_levels_train_workspace_bytes
-        elif self.gated:  # `heads` takes the place of `pooling` in both calls
-            pool, query = self.heads, self.lib.hipac_mil_gated_train_workspace_bytes
-        elif self.heads > 1:
-            pool, query = self.heads, self.lib.hipac_mil_heads_train_workspace_bytes
-        else:
-            query = self.lib.hipac_mil_dropout_train_workspace_bytes if self.dropout > 0.0 else self.lib.hipac_mil_train_workspace_bytes
-        need = query(C.addressof(self._p), pool, n, n_bags)
+        query_name, step_name, first, extra, attn_1d = self._entry
+        need = getattr(self.lib, query_name)(C.addressof(self._p), first, n, n_bags)
         if need == 0:
             raise capi.HipacError(f"mil training step of {n} rows in {n_bags} bags refused (sizes outside the kernel's limits)")
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         logits = torch.empty((n_bags, self.C), dtype=torch.float32, device=self.device)
-        one = (self.heads == 1 and not self.gated) or self.levels is not None
-        self.attn = torch.empty(n if one else (n, self.heads), dtype=torch.float32, device=self.device) \
+        self.attn = torch.empty(n if attn_1d else (n, self.heads), dtype=torch.float32, device=self.device) \
             if (want_attn and self.pooling == "attention") else None
-        args = (C.addressof(self._p), pool, feats.data_ptr(), N, capi._ptr(rows_dev), offs_dev.data_ptr(), n, n_bags,
-                lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
-                capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0)
+        level = () if lv_dev is None else (lv_dev.data_ptr(),)  # level_of goes in after rows
         with torch.cuda.device(self.device):
-            if self.levels is not None:  # level_of goes in after rows
-                rc = self.lib.hipac_mil_levels_train_fwd_bwd(*args[:5], lv_dev.data_ptr(), *args[5:], capi._stream())
-            elif self.gated:
-                rc = self.lib.hipac_mil_gated_train_fwd_bwd(*args, capi._stream())
-            elif self.heads > 1:
-                rc = self.lib.hipac_mil_heads_train_fwd_bwd(*args, capi._stream())
-            elif self.dropout > 0.0:
-                rc = self.lib.hipac_mil_dropout_train_fwd_bwd(*args, self.dropout, self.seed, self.steps & 0xFFFFFFFF, capi._stream())
-            else:
-                rc = self.lib.hipac_mil_train_fwd_bwd(*args, capi._stream())
-        capi._check(rc, "hipac_mil_levels_train_fwd_bwd" if self.levels is not None else "hipac_mil_gated_train_fwd_bwd" if self.gated else "hipac_mil_heads_train_fwd_bwd" if self.heads > 1 else
-                    "hipac_mil_dropout_train_fwd_bwd" if self.dropout > 0.0 else "hipac_mil_train_fwd_bwd")
+            rc = getattr(self.lib, step_name)(
+                C.addressof(self._p), first, feats.data_ptr(), N, capi._ptr(rows_dev), *level, offs_dev.data_ptr(), n, n_bags,
+                lab.data_ptr(), capi._ptr(self.class_weights), C.addressof(self._g), loss.data_ptr(), logits.data_ptr(),
+                capi._ptr(self.attn), self._ws.data_ptr(), self._ws.numel(), 1 if accumulate else 0, *extra(), capi._stream())
+        capi._check(rc, step_name)
         return loss, logits
 
     def step(self, feats, rows, offsets, labels, level_of=None) -> Tuple[torch.Tensor, torch.Tensor]:
