@@ -345,7 +345,8 @@ int hipac_train_amp_encoder_forward(const float* params, float* stats, const flo
                                     float eps, float* feats, void* workspace, size_t workspace_bytes, void* stream);
 int hipac_train_amp_encoder_backward(const float* params, const float* dfeats, int batch, float* grads, int accumulate,
                                      void* workspace, size_t workspace_bytes, void* stream);
-/* grads[i] *= inv_scale; found_inf[0] (device int32, zeroed by the caller) becomes 1 when a gradient is inf / nan. */
+/* grads[i] *= inv_scale; found_inf[0] (device int32, zeroed by the caller) becomes 1 when a product is inf / nan --
+ * exactly that: every finite float32, FLT_MAX included, leaves the flag alone. */
 int hipac_grads_unscale_check(float* grads, int64_t n, float inv_scale, int32_t* found_inf, void* stream);
 
 /* Baseline-JPEG tiles of a tiled pyramidal TIFF decoded on the device, straight into a level image in HBM -- what

@@ -163,14 +163,15 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(const h16* __restrict__ 
   }
 }
 
-// grads *= inv_scale; flag[0] = 1 when a gradient is not finite (GradScaler.unscale_)
+// grads *= inv_scale; flag[0] = 1 when an unscaled gradient is inf / nan (GradScaler.unscale_).  Every finite float passes,
+// FLT_MAX included: the comparison is against FLT_MAX itself, which only inf and nan fail
 __global__ __launch_bounds__(256) void unscale_check_kernel(float* __restrict__ g, long long n, float inv_scale,
                                                             int* __restrict__ flag) {
   bool bad = false;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const float v = g[i] * inv_scale;
     g[i] = v;
-    bad |= !(fabsf(v) <= 3.0e38f);
+    bad |= !(fabsf(v) <= 3.402823466e+38f);
   }
   if (bad) atomicOr(flag, 1);
 }
