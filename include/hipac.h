@@ -213,9 +213,10 @@ int hipac_tile_preprocess(const uint8_t* level, int W, int H, int64_t pitch, int
  * window's resampled pixels are a gather from ONE resampled image of the level, so each
  * source pixel is read once per level instead of once per overlapping window (up to 64x at
  * level 0).  Same arithmetic as hipac_tile_preprocess, bit for bit.
- *   hipac_level_planes_sizes  : bytes of the three caller-owned scratch buffers
- *   hipac_level_build_planes  : level (RGB, 3 B/px, 4-byte aligned base and pitch) -> himg, dimg,
- *                               cells (sums of the 224x224 source cells, for the whiteness test)
+ *   hipac_level_planes_sizes  : bytes of the caller-owned buffers dimg and cells (*himg_bytes = 0)
+ *   hipac_level_build_planes  : level (RGB, 3 B/px, 4-byte aligned base and pitch) -> dimg, cells
+ *                               (sums of the 224x224 source cells, for the whiteness test)
+ *                               himg: unused since the one-pass kernel; may be NULL
  *   hipac_level_window_stats  : per window sum of the padded PxPx3 pixels and keep flag
  *                               (replaces np.mean(patch) > 240, src/main.py:718-720)
  *   hipac_level_gather        : uint8[n,224,224,3] resized pixels of the listed windows

@@ -485,23 +485,18 @@ class LevelPlanes:
         lib = load_library()
         H, Wp, _ = level.shape
         self.W, self.H, self.P = (Wp if width is None else int(width)), H, P
-        hb, db, cb = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        _check(lib.hipac_level_planes_sizes(self.W, self.H, P, C.byref(hb), C.byref(db), C.byref(cb)),
+        db, cb = C.c_size_t(), C.c_size_t()
+        _check(lib.hipac_level_planes_sizes(self.W, self.H, P, None, C.byref(db), C.byref(cb)),
                "hipac_level_planes_sizes")
         dev = level.device
-        himg = torch.empty(hb.value, dtype=torch.uint8, device=dev)  # only needed while building
         self.dimg = torch.empty(db.value, dtype=torch.uint8, device=dev)
         self.cells = torch.empty(cb.value // 4, dtype=torch.int32, device=dev)
         b, k, ksize = device_tables(P, dev)
         with torch.cuda.device(dev):
             rc = lib.hipac_level_build_planes(level.data_ptr(), self.W, self.H, Wp * 3, P, b.data_ptr(), k.data_ptr(),
-                                              ksize, himg.data_ptr(), self.dimg.data_ptr(), self.cells.data_ptr(),
-                                              _stream())
+                                              ksize, None, self.dimg.data_ptr(), self.cells.data_ptr(), _stream())
         _check(rc, "hipac_level_build_planes")
         self._lib, self.device = lib, dev
-        himg.record_stream(torch.cuda.current_stream(dev))
-        if os.environ.get("HIPAC_KEEP_HIMG"):
-            self.himg = himg  # debugging aid
 
     def stats(self, xy: torch.Tensor):
         n = xy.shape[0]

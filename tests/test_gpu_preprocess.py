@@ -164,6 +164,51 @@ def test_level_planes_equal_per_window_kernel(P):
     assert 0 < int(keep.sum()) < len(keep)
 
 
+@pytest.mark.parametrize("P", [448, 896, 1792])
+def test_level_planes_allocates_only_d_image_and_cells(P):
+    """Building a level allocates the D image and the cell sums and nothing else (the intermediate image of a
+    horizontal pass, 4-16 MB at these sizes, is gone): peak minus baseline <= their bytes + 64 KiB.  The figure is the
+    allocator's count of the bytes ASKED of it.  Its count of the bytes handed out also rounds a block to 512 B, but a
+    cached block up to 1 MiB larger than the request is reused whole, so that count depends on what earlier tests
+    left in the cache (seen: 2 932 224 B handed out for the 2 064 480 B D image of P = 896)."""
+    H, W = 2 * P + 300, 2 * P + 77
+    lv = torch.randint(0, 256, (H, (W + 15) // 16 * 16, 3), dtype=torch.uint8, device="cuda")
+    capi.LevelPlanes(lv, P, width=W)  # warm-up: the coefficient tables are cached on the device
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base, base_out = torch.cuda.memory_stats()["requested_bytes.all.current"], torch.cuda.memory_allocated()
+    planes = capi.LevelPlanes(lv, P, width=W)
+    torch.cuda.synchronize()
+    grown = torch.cuda.memory_stats()["requested_bytes.all.peak"] - base
+    print(f"P={P}: peak - baseline {grown} B asked, {torch.cuda.max_memory_allocated() - base_out} B handed out; "
+          f"dimg {planes.dimg.numel()} B, cells {4 * planes.cells.numel()} B")
+    assert grown <= planes.dimg.numel() + 4 * planes.cells.numel() + 64 * 1024
+
+
+@pytest.mark.parametrize("W,H", [(1, 1), (9, 113), (225, 224), (224, 225), (449, 337)])
+@pytest.mark.parametrize("P", [448, 896, 1792])
+def test_level_planes_small_geometries(P, W, H):
+    """The whole-level resampler == the per-window kernel, bit for bit, at the smallest geometries that reach its
+    boundaries: (1, 1) one partial group, one strip, every halo row outside; (9, 113) the group boundary and the strip
+    boundary at 112 owned rows; (225, 224) a second window column / cell with exactly one cell row; (224, 225) its
+    transpose; (449, 337) three window columns and four strips, ragged on both edges.  The row pitch is W rounded up to
+    16 pixels and the padding columns are 0, so a read past W shows against the expected white."""
+    rng = np.random.RandomState(1000 * W + H + P)
+    img = torch.zeros((H, (W + 15) // 16 * 16, 3), dtype=torch.uint8)
+    img[:, :W] = torch.from_numpy(rng.randint(0, 256, (H, W, 3), dtype=np.uint8))
+    lv = img.cuda()
+    xs = np.arange(0, W, 224)
+    ys = np.arange(0, H, 224)
+    xy = torch.from_numpy(np.stack([np.repeat(xs, len(ys)), np.tile(ys, len(xs))], 1).astype(np.int32)).cuda()
+    ref_u8, ref_sums, ref_keep = capi.tile_preprocess(lv, xy, P, "u8", width=W)
+    planes = capi.LevelPlanes(lv, P, width=W)
+    sums, keep = planes.stats(xy)
+    assert torch.equal(sums, ref_sums) and torch.equal(keep, ref_keep)
+    got = planes.gather(xy)
+    same = (got == ref_u8).flatten(1).all(1)
+    assert bool(same.all()), f"{int((~same).sum())} of {len(same)} windows differ, first {int((~same).nonzero()[0])}"
+
+
 def test_iter_level_planes_and_windows_paths_agree(slide):
     for level in (0, 1, 2):
         a = list(extract.iter_level(slide, level, out_format="u8", batch_windows=50, use_planes=True))
