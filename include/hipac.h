@@ -28,8 +28,10 @@
  *   - a handle belongs to the device that was current in hipac_resnet18_pack;
  *     calling it with another device current returns HIPAC_EINVAL
  *   - developer knobs (HIPAC_SUBBATCH, HIPAC_GROUP, HIPAC_LANES, HIPAC_FUSE_STEM,
- *     HIPAC_STEM_STRIP) are read from the environment on every call; they select
+ *     HIPAC_STEM_STRIP, HIPAC_JPEG_LANES) are read from the environment on every call; they select
  *     among equivalent schedules and must not change while calls are in flight
+ *     (HIPAC_JPEG_LANES = 1..64: tiles per wave of hipac_jpeg_decode_tiles' Huffman kernel, instead of
+ *     ceil(tiles / 16384); any other value is ignored)
  */
 #ifndef HIPAC_H_
 #define HIPAC_H_

@@ -361,7 +361,7 @@ struct HostTables {
   bool h_ok[2][4];
 };
 struct HostFrame {
-  int w, h, nc, dri, adobe;
+  int w, h, nc, dri, adobe, jfif;
   int id[3], hs[3], vs[3], tq[3], td[3], ta[3];
   long long scan;  // offset of the entropy-coded data, -1: none seen
 };
@@ -426,6 +426,8 @@ static int parse_stream(const unsigned char* p, long long n, HostTables& T, Host
     } else if (m == 0xDD) {
       if (sl < 2) return -1;
       F.dri = be16(s);
+    } else if (m == 0xE0) {
+      if (sl >= 14 && std::memcmp(s, "JFIF", 5) == 0) F.jfif = 1;
     } else if (m == 0xEE) {
       if (sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) F.adobe = s[11];
     } else if (m == 0xDA) {
@@ -592,8 +594,9 @@ int hipac_jpeg_decode_tiles(const uint8_t* file_host, const uint8_t* file_dev, i
     if (!ok) continue;
     const int hmax = F.hs[0], vmax = F.vs[0];
     c.mcus_x = tile_w / (8 * hmax), c.mcus_y = tile_h / (8 * vmax), c.dri = F.dri;
-    // TIFF photometric 6 = YCbCr samples; 2 = RGB samples in the JPEG stream (an Adobe marker with transform 0 says the same)
-    c.convert = (L.photometric == 6 && F.adobe != 0) ? 1 : 0;
+    // TIFF photometric 6 = YCbCr samples; 2 = RGB samples in the JPEG stream.  Under 6, an Adobe marker with transform 0 says
+    // RGB as well -- unless the stream is JFIF, which libjpeg takes as YCbCr before it looks at Adobe (jdapimin.c)
+    c.convert = (L.photometric == 6 && (F.jfif || F.adobe != 0)) ? 1 : 0;
     int blk = 0, pl = 0, mb = 0;
     for (int k = 0; k < 3; ++k) {
       c.bw[k] = c.mcus_x * F.hs[k], c.bh[k] = c.mcus_y * F.vs[k];

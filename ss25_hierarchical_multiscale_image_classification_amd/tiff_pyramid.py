@@ -516,6 +516,27 @@ def _adobe_rgb_marker() -> bytes:
     return b"\xff\xee\x00\x0eAdobe\x00\x64\x00\x00\x00\x00\x00"
 
 
+def _jpeg_tile_stream(raw: bytes, jpeg_tables: Optional[bytes], photometric: int) -> bytes:
+    """The complete JPEG stream the host decoder is given for the tile bytes ``raw`` of a directory with that JPEGTables tag
+    and photometric tag.  Photometric 2 says the three components ARE R, G, B (what libtiff tells libjpeg, whatever markers
+    the tile carries): the stream gets an Adobe marker with transform 0, and loses a JFIF APP0 -- libjpeg takes JFIF as
+    "YCbCr" before it looks at Adobe -- and an Adobe marker of its own, which would be read after the inserted one."""
+    data = raw
+    if jpeg_tables:
+        tb = jpeg_tables
+        data = tb[:-2] + raw[2:] if tb[-2:] == b"\xff\xd9" and raw[:2] == b"\xff\xd8" else raw
+    if photometric != 2 or data[:2] != b"\xff\xd8":
+        return data
+    out, pos = [data[:2], _adobe_rgb_marker()], 2
+    while pos + 4 <= len(data) and data[pos] == 0xFF and data[pos + 1] not in (0xDA, 0xD9, 0xFF):
+        end = pos + 2 + int.from_bytes(data[pos + 2:pos + 4], "big")
+        seg = data[pos:end]
+        if not (seg[1] == 0xE0 and seg[4:9] == b"JFIF\x00") and not (seg[1] == 0xEE and seg[4:9] == b"Adobe"):
+            out.append(seg)
+        pos = end
+    return b"".join(out) + data[pos:]
+
+
 class TiffPyramid:
     """Tiled TIFF pyramid.  ``level_dimensions`` / ``level_downsamples`` as in openslide."""
 
@@ -572,13 +593,7 @@ class TiffPyramid:
         else:
             from PIL import Image
 
-            data = raw
-            if lv.jpeg_tables:
-                tb = lv.jpeg_tables
-                data = tb[:-2] + raw[2:] if tb[-2:] == b"\xff\xd9" and raw[:2] == b"\xff\xd8" else raw
-            if lv.photometric == 2:  # RGB stored in the JPEG: keep Pillow from applying YCbCr -> RGB
-                data = data[:2] + _adobe_rgb_marker() + data[2:]
-            im = Image.open(io.BytesIO(data))
+            im = Image.open(io.BytesIO(_jpeg_tile_stream(raw, lv.jpeg_tables, lv.photometric)))
             im.load()
             a = np.asarray(im.convert("L"))[:, :, None] if lv.samples == 1 else np.asarray(im.convert("RGB"))
             if a.shape[0] != lv.tile_h or a.shape[1] != lv.tile_w:
