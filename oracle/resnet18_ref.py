@@ -96,16 +96,20 @@ def basic_block(x, sd, prefix: str, stride: int, taps: Optional[dict] = None):
 
 @torch.no_grad()
 def resnet18_forward(
-    x: torch.Tensor, sd: Dict[str, torch.Tensor], taps: Optional[dict] = None
+    x: torch.Tensor, sd: Dict[str, torch.Tensor], taps: Optional[dict] = None, dtype: torch.dtype = torch.float32
 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """x: float32[B,3,224,224] NCHW, ImageNet-normalised.
 
     Returns (features float32[B,512], logits float32[B,C] or None when the
     state dict has no fc).  ``taps`` (optional dict) receives every
     intermediate activation, NCHW fp32, for layer-wise parity tests.
+    ``dtype=torch.float64`` evaluates the same graph in float64 (x and every
+    tensor of ``sd`` are converted).
     """
     sd = canonical_state_dict(sd)
-    x = x.to(torch.float32)
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
+    x = x.to(dtype)
     y = F.conv2d(x, sd["conv1.weight"], None, stride=2, padding=3)
     y = F.relu(_bn(y, sd, "bn1"))
     if taps is not None:
