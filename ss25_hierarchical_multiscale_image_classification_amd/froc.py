@@ -13,7 +13,8 @@ quirks decide the numbers:
 
 Additions: ``froc_score`` (the challenge's six-point score, the mean sensitivity at 1/4 .. 8 FPs per slide), the mask
 sources of ``load_case_mask`` (grayscale tiled TIFF masks or the XML annotations rasterised with the extractor's rule)
-and ``run_evaluation``, the CLI body, which also writes ``froc_results.json`` (and ``froc.png``).
+and ``run_evaluation``, the CLI body, which also writes ``froc_results.json`` (and ``froc.png``).  The slide-level ROC and the
+bootstrap intervals of ``--eval_roc`` / ``--eval_bootstrap`` are in ``froc_ci.py``.
 """
 from __future__ import annotations
 
@@ -302,9 +303,17 @@ def froc_results(names, FROC_data, detection_summaries, FP_summaries, total_FPs,
 
 
 def run_evaluation(data_root: str, cwd: Optional[str] = None, resolution: float = L0_RESOLUTION,
-                   level: int = EVALUATION_MASK_LEVEL) -> int:
+                   level: int = EVALUATION_MASK_LEVEL, *, eval_roc: bool = False, slide_scores: Optional[str] = None,
+                   bootstrap: int = 0, ci: float = 95.0, seed: int = 0) -> int:
     """``--run_evaluation``: score ``cwd/models/first_model/model_predictions_csv/*.csv`` against the masks under
-    ``data_root/test/mask``; print the curve and the score, write froc_results.json (and froc.png) into ``cwd``."""
+    ``data_root/test/mask``; print the curve and the score, write froc_results.json (and froc.png) into ``cwd``.
+    ``eval_roc`` adds the slide-level ROC of the same cases (roc_results.json, roc.png; the score of a case is its largest
+    detection probability, or its entry in the file ``slide_scores``), ``bootstrap`` > 0 the percentile intervals at ``ci``
+    percent over that many resamples of the cases keyed by ``seed`` (bootstrap_results.json): ``froc_ci.py``.  Without
+    them nothing else is written or printed."""
+    from . import froc_ci
+
+    froc_ci.check_options(bootstrap, ci)
     cwd = os.getcwd() if cwd is None else cwd
     print("[INFO] Running CAMELYON16 evaluation script.")
     mask_folder = os.path.join(data_root, "test", "mask")
@@ -316,6 +325,7 @@ def run_evaluation(data_root: str, cwd: Optional[str] = None, resolution: float 
         print(f"[ERROR] Model results folder '{results_folder}' not found. Please run your detection model first.")
         return 1
     names, fps, tps, ntum, dets, fpsum = [], [], [], [], [], []
+    labels, max_probs = [], []  # the slide-level ROC's inputs, over the same cases
     for file in sorted(f for f in os.listdir(results_folder) if f.endswith(".csv")):
         case = file[:-4]
         print(f"Evaluating Performance on image: {case}", flush=True)
@@ -336,6 +346,7 @@ def run_evaluation(data_root: str, cwd: Optional[str] = None, resolution: float 
             itc = computeITCList(em, resolution, level)
         f, t, k, d, s = compute_FP_TP_Probs(Ycorr, Xcorr, Probs, is_tumor, em, itc, level)
         names.append(file), fps.append(f), tps.append(t), ntum.append(k), dets.append(d), fpsum.append(s)
+        labels.append(int(is_tumor)), max_probs.append(max(Probs) if Probs else 0.0)
     if not names:
         print("[WARNING] No cases processed for FROC evaluation.")
         return 0
@@ -349,4 +360,7 @@ def run_evaluation(data_root: str, cwd: Optional[str] = None, resolution: float 
           f"{len(total_FPs)} points, sensitivity {float(total_sensitivity[0]):.4f} at {float(total_FPs[0]):.3f} FPs per slide")
     print(f"[INFO] CAMELYON16 score (mean sensitivity at 1/4, 1/2, 1, 2, 4, 8 FPs per slide): {res['froc_score']:.4f}")
     print(f"[INFO] Results written to froc_results.json{' and froc.png' if plotted else ''}")
+    if eval_roc or bootstrap:
+        return froc_ci.run(cwd, [n[:-4] for n in names], FROC_data, labels, max_probs, total_FPs, total_sensitivity, res["froc_score"],
+                           eval_roc=eval_roc, slide_scores_path=slide_scores, bootstrap=bootstrap, ci=ci, seed=seed)
     return 0

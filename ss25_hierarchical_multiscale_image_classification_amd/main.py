@@ -43,6 +43,10 @@ slide route and ``--detect``.  The Otsu mask is made from the original pixels an
 ``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by ``--detect``, or by
 ``features.save_froc_csv`` with one line per window) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
+``--eval_roc`` adds the slide-level ROC and AUC of the same cases (``roc_results.json``, ``roc.png``; scores from the CSVs or
+from ``--eval_slide_scores FILE``), ``--eval_bootstrap B`` the ``--eval_ci`` percent percentile-bootstrap intervals of the
+score, its six sensitivities and the AUC over B resamples of the cases, drawn and scanned on the device and keyed by
+``--seed`` (``froc_ci.py`` -> ``bootstrap_results.json``).  Without them every byte stays as it was.
 
 ``--train_mil`` trains the ABMIL slide classifier (``mil_train.py``, the loop of the reference's
 ``experiments/experiment_configs.yaml``) on the ``patch_features_L.npy`` / ``patch_labels_L.npy`` / ``patch_paths_L.txt``
@@ -81,6 +85,20 @@ OUT_OF_SCOPE = ("download", "remote", "prepare", "validation", "evaluate",
                 "check_good_downloaded_files")
 
 
+def _eval_bootstrap(text: str) -> int:
+    v = int(text)
+    if not 0 <= v <= 65536:
+        raise argparse.ArgumentTypeError(f"takes 0 (off) .. 65536 replicates, got {v}")
+    return v
+
+
+def _eval_ci(text: str) -> float:
+    v = float(text)
+    if not 0.0 < v < 100.0:
+        raise argparse.ArgumentTypeError(f"takes a percentage above 0 and below 100, got {text}")
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="HiPAC hot path on MI355X (patch extraction + ResNet18 scoring)")
     # --- the reference's surface (src/main.py:1075-1093) ---
@@ -93,6 +111,15 @@ def build_parser() -> argparse.ArgumentParser:
                    choices=["balanced", "weighted_loss", "self_supervised"])
     p.add_argument("--run_evaluation", action="store_true",
                    help="CAMELYON16 FROC evaluation of the detection CSVs (src/main.py:1168-1225)")
+    p.add_argument("--eval_roc", action="store_true",
+                   help="--run_evaluation: also the slide-level ROC and its AUC over the evaluated cases -> roc_results.json (and "
+                        "roc.png); a case's score is its largest detection probability")
+    p.add_argument("--eval_slide_scores", type=str, default=None, metavar="FILE",
+                   help="--eval_roc: take the scores from FILE, lines 'case,score[,...]' (results/mil_predictions.csv fits)")
+    p.add_argument("--eval_bootstrap", type=_eval_bootstrap, default=0, metavar="B",
+                   help="--run_evaluation: percentile-bootstrap intervals of the score, the six sensitivities (and the AUC) over B "
+                        "resamples of the cases, drawn on the device and keyed by --seed -> bootstrap_results.json (0 = off, at most 65536)")
+    p.add_argument("--eval_ci", type=_eval_ci, default=95.0, metavar="PCT", help="--eval_bootstrap: the interval in percent (above 0, below 100)")
     p.add_argument("--validate", action="store_true",
                    help="sanity check of the feature files of --patch_level in the working directory (src/main.py:1017-1070): "
                         "PCA and a logistic-regression probe on the device -> results/validate_<L>.json (rank 0)")
@@ -514,7 +541,8 @@ def cmd_run_evaluation(args):
     rank, _ = rank_world()
     if rank != 0:  # the evaluation is not sharded: rank 0 does it
         return 0
-    return run_evaluation(data_root(args))
+    return run_evaluation(data_root(args), eval_roc=args.eval_roc, slide_scores=args.eval_slide_scores, bootstrap=args.eval_bootstrap,
+                          ci=args.eval_ci, seed=0 if args.seed is None else args.seed)
 
 
 def mil_triple(args):
