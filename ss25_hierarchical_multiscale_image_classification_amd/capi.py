@@ -140,6 +140,17 @@ SYMBOLS = {
                                   C.c_float, C.c_int, C.c_void_p]),
 }
 
+# include/hipac_pair_tap.h (raw taps of the pair modes; tests only): its own version number and symbol list
+# (tests/test_pair_tap_capi_symbols.py)
+PAIR_TAP_ABI_VERSION = 1
+PAIR_TAP_POOL, PAIR_TAP_BLOCK0, PAIR_TAP_INNER0 = 1, 2, 10
+PAIR_TAP_PLANE_PAIRS, PAIR_TAP_PLANE_Q8 = 0, 1
+PAIR_TAP_SYMBOLS = {
+    "hipac_pair_tap_abi_version": (C.c_int, []),
+    "hipac_pair_tap_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hipac_pair_tap_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -171,6 +182,7 @@ def load_library(path: Optional[os.PathLike] = None):
             )
         lib = C.CDLL(str(p))
         bind_symbols(lib, SYMBOLS, "hipac_abi_version", ABI_VERSION, "ABI")
+        bind_symbols(lib, PAIR_TAP_SYMBOLS, "hipac_pair_tap_abi_version", PAIR_TAP_ABI_VERSION, "pair tap ABI")
         if path is None:
             _lib = lib
         return lib
@@ -407,6 +419,24 @@ class PackedResNet18:
         with torch.cuda.device(dst.device):
             _check(self._lib.hipac_resnet18_tap(self.handle, self._ws.data_ptr(), batch, tap, dst.data_ptr(), _stream()),
                    "hipac_resnet18_tap")
+        return dst
+
+    def raw_tap(self, batch: int, map_: int, plane: int = PAIR_TAP_PLANE_PAIRS) -> torch.Tensor:
+        """The stored bytes of one map of the last forward (include/hipac_pair_tap.h; pair modes, tests only): uint8
+        [batch, H, H, bytes per pixel], a plain device-to-device copy.  ``map_``: PAIR_TAP_POOL, PAIR_TAP_BLOCK0 + b,
+        PAIR_TAP_INNER0 + b (valid right after ``run_ops`` of block b's first conv alone); ``plane``: the pair tensor
+        (block 7: the fp32 map) or fp16q8's e4m3 byte tensor."""
+        prec = self._lib.hipac_weights_precision(self.handle)
+        if self._ws is None or batch < 1 or self._lib.hipac_resnet18_workspace_bytes(batch, prec) > self._ws.numel():
+            raise HipacError(f"raw_tap: batch {batch} does not fit the workspace of the last forward")
+        need = self._lib.hipac_pair_tap_bytes(batch, prec, map_, plane)
+        if need == 0:
+            raise HipacError(f"raw_tap: precision {self.precision} has no map {map_}, plane {plane}")
+        h = (56, 56, 28, 28, 14, 14, 7, 7)[(map_ - PAIR_TAP_BLOCK0) % 8] if map_ >= PAIR_TAP_BLOCK0 else 56
+        dst = torch.empty((batch, h, h, need // (batch * h * h)), dtype=torch.uint8, device=self._ws.device)
+        with torch.cuda.device(dst.device):
+            _check(self._lib.hipac_pair_tap_copy(self.handle, self._ws.data_ptr(), batch, map_, plane, dst.data_ptr(), need, _stream()),
+                   "hipac_pair_tap_copy")
         return dst
 
 

@@ -1,6 +1,7 @@
 // The ResNet18 forward driver of the C ABI: workspace plan, the split of a batch into sub-batches, groups and
 // launch lanes, and the entry points that run the trunk (forward, run_ops, tap).
 #include "resnet_handle.h"
+#include "../../include/hipac_pair_tap.h"
 
 namespace hipac {
 
@@ -104,6 +105,35 @@ static bool apply_input_layout(Plan& p, int precision, int in_layout) {
   const bool stem_takes_u8 = pair_mode(precision) ? p.stem_strip : p.fuse_stem;
   p.u8_input = in_layout == HIPAC_IN_U8_HWC && stem_takes_u8;
   return in_layout == HIPAC_IN_NCHW_F32 || (in_layout == HIPAC_IN_U8_HWC && !p.u8_input);
+}
+
+// include/hipac_pair_tap.h: where (map, plane) lies in the workspace of plan p, and how many bytes `batch` images of it are.
+// false for a combination the header refuses.
+struct PairTapSpan {
+  size_t off, bytes;
+};
+static bool pair_tap_span(const Plan& p, int precision, int batch, int map, int plane, PairTapSpan* out) {
+  if (batch < 1 || !pair_mode(precision)) return false;
+  if (map < HIPAC_PAIR_TAP_POOL || map > HIPAC_PAIR_TAP_INNER0 + 7) return false;
+  if (plane != HIPAC_PAIR_TAP_PLANE_PAIRS && plane != HIPAC_PAIR_TAP_PLANE_Q8) return false;
+  const bool last = map == HIPAC_PAIR_TAP_BLOCK0 + 7;
+  if (plane == HIPAC_PAIR_TAP_PLANE_Q8 && (precision != HIPAC_PREC_FP16Q8 || last)) return false;
+  const int ch[4] = {64, 128, 256, 512}, hw[4] = {56, 28, 14, 7};
+  size_t pairs;  // offset of the pair tensor (map 9: of the fp32 map)
+  int st = 0;
+  if (map == HIPAC_PAIR_TAP_POOL) {
+    pairs = p.pool;
+  } else if (map < HIPAC_PAIR_TAP_INNER0) {
+    st = (map - HIPAC_PAIR_TAP_BLOCK0) / 2;
+    pairs = p.blk[map - HIPAC_PAIR_TAP_BLOCK0];
+  } else {
+    st = (map - HIPAC_PAIR_TAP_INNER0) / 2;
+    pairs = st < 2 ? p.tmp_e : p.tmp_l;
+  }
+  const size_t elems = (size_t)batch * hw[st] * hw[st] * ch[st];
+  if (plane == HIPAC_PAIR_TAP_PLANE_Q8) *out = {p.q8 + pairs / 2, elems * 2};  // Q8Map::of (conv_launch.h)
+  else *out = {pairs, elems * 4};                                             // a pair or one float per element
+  return true;
 }
 
 }  // namespace hipac
@@ -271,6 +301,37 @@ int hipac_resnet18_tap(const hipac_weights_t* w, const void* workspace, int batc
   }
   int rc = launch_tap_export(src, is_f32, w->net.precision, batch, C, H, H, dst, (hipStream_t)stream);
   HIPAC_REQUIRE(rc == 0, rc, "tap: launch failed (%d)", rc);
+  return 0;
+}
+
+int hipac_pair_tap_abi_version(void) { return HIPAC_PAIR_TAP_ABI_VERSION; }
+
+size_t hipac_pair_tap_bytes(int batch, int precision, int map, int plane) {
+  PairTapSpan sp;
+  if (batch < 1 || !pair_mode(precision)) return 0;
+  return pair_tap_span(make_plan(batch, precision), precision, batch, map, plane, &sp) ? sp.bytes : 0;
+}
+
+int hipac_pair_tap_copy(const hipac_weights_t* w, void* workspace, int batch, int map, int plane, void* dst,
+                        size_t dst_bytes, void* stream) {
+  HIPAC_REQUIRE(w && workspace && dst, HIPAC_EINVAL, "pair_tap: null argument");
+  const int precision = w->net.precision;
+  HIPAC_REQUIRE(pair_mode(precision), HIPAC_EUNSUPPORTED, "pair_tap: the handle is no pair mode (fp16x3, fp16q8)");
+  HIPAC_REQUIRE(batch > 0, HIPAC_EINVAL, "pair_tap: batch %d", batch);
+  const Plan p = make_plan(batch, precision);
+  HIPAC_REQUIRE(batch <= p.bc, HIPAC_EINVAL, "pair_tap: batch %d exceeds one sub-batch (%d)", batch, p.bc);
+  PairTapSpan sp;
+  HIPAC_REQUIRE(pair_tap_span(p, precision, batch, map, plane, &sp), HIPAC_EINVAL, "pair_tap: map %d, plane %d", map, plane);
+  HIPAC_REQUIRE(dst_bytes == sp.bytes, HIPAC_EINVAL, "pair_tap: dst holds %zu bytes, the plane has %zu", dst_bytes, sp.bytes);
+  HIPAC_REQUIRE(sp.off + sp.bytes <= p.total, HIPAC_EINVAL, "pair_tap: the plane lies outside the workspace plan");
+  if (map == HIPAC_PAIR_TAP_BLOCK0 + 7 && p.pool_head) {
+    // the forward left the pooled partial sums, not the map: the last conv once more with its fp32-map epilogue (as tap 9)
+    Plan q = p;
+    q.pool_head = 0;
+    int rc_t = trunk_for(precision)(w->net, q, (char*)workspace, nullptr, 0, 0, batch, (hipStream_t)stream, kNumOps - 1, kNumOps - 1);
+    HIPAC_REQUIRE(rc_t == 0, rc_t, "pair_tap: re-running the last conv failed (%d)", rc_t);
+  }
+  HIPAC_CHECK_HIP(hipMemcpyAsync(dst, (const char*)workspace + sp.off, sp.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 

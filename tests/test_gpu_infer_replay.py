@@ -24,7 +24,8 @@ All patches go to the device; the listed images are replayed on the CPU one at a
                           HIPAC_POOL_HEAD=0
   fp32         nchw_f32   default                    2: all             conv_f32.hip, u = 2^-24
 Asserted: every stage's ratio <= 1 (no element outside its interval), every block's mean-square statistic below its gate, and
-labels == argmax(device logits).  fp16x3 and fp16q8 are out of scope (the oracle's docstring says why).
+labels == argmax(device logits).  fp16x3 and fp16q8 are replayed conv by conv in
+tests/test_gpu_pair_replay.py (the oracle's docstring says why they need another method).
 
 Every figure is printed by the test (ratio / fig / sqrtK / msq per stage).  Measured on an MI355X, worst case of each
 precision, with the float32 stand-in of tests/infer_replay_cases.py on the same cases in brackets:
