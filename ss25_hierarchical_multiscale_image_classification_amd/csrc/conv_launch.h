@@ -43,14 +43,12 @@ template <int BM_, int BN_, int NSTAGE_> struct GldsTile {  // conv_glds_kernel'
 template <int COUT> struct TileCfg : GldsTile<HIPAC_BM_A, (COUT % HIPAC_BN_A == 0 ? HIPAC_BN_A : 128), HIPAC_NSTAGE_A> {};
 template <> struct TileCfg<64> : GldsTile<HIPAC_BM_64, 64, HIPAC_NSTAGE_B> {};
 
-// dynamic LDS of the stride-1 halo16 kernel: the band, then the deepest weight ring (NSW slots) that keeps two workgroups per
-// CU, or the kernel's STG_BYTES if that is larger (its S_BYTES)
-template <int W, int BM, int BN>
+// the stride-1 halo16 kernel's weight ring: the deepest (NSW slots) that keeps two workgroups per CU; its dynamic LDS (band,
+// ring, bias) is halo16_lds_bytes' (halo16.h)
+template <int W, int BM, int BN, int COUT>
 struct Halo16Lds {
-  static constexpr int A_BYTES = halo_band_pieces(W, BM) * 1024;
-  static constexpr int STG = 4 * 32 * (BN / 2 * 4 + 16);
-  static constexpr int NSW = (A_BYTES + 3 * BN * 128 <= 80 * 1024) ? 3 : 2;
-  static constexpr int LDS = A_BYTES + (NSW * BN * 128 > STG ? NSW * BN * 128 : STG);
+  static constexpr int NSW = halo16_lds_bytes(W, BM, BN, 3, COUT) <= 80 * 1024 ? 3 : 2;
+  static constexpr int LDS = halo16_lds_bytes(W, BM, BN, NSW, COUT);
 };
 
 // The grid of the tiled kernels (conv_glds_kernel, the halo kernels) is 1-D and decoded XCD-aware: virtual block v is pixel tile
@@ -98,8 +96,7 @@ static int launch_conv(const void* in, const ConvW& w, const void* resid, void* 
   } else if constexpr (KS == 3 && STRIDE == 2 && !OUTF32 && !RESID && COUT % 128 == 0 && HI == WI) {
     // the entry convs of layers 2-4 on halo16's stride-2 form: four parity-plane bands per 64-channel chunk
     constexpr int BM = 256, BN = 128, NSW = 2;
-    constexpr int LDS = halo_band_pieces(HO, BM) * 1024 + NSW * BN * 128;
-    static_assert(LDS <= 80 * 1024, "two workgroups per CU");
+    constexpr int LDS = halo16_lds_bytes(WO, BM, BN, NSW, COUT);
     constexpr auto kern = conv3x3_halo16_kernel<T, CIN, COUT, HO, WO, BM, BN, NSW, RELU, false, false, 0, false, true>;
     const TileGrid g = tile_grid(M, BM, COUT / BN, HIPAC_HALO_GRID);
     return launch_dyn_lds<kern>(g.blocks, 256, LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)nullptr, out, M, n, g.n_mtiles,
@@ -108,7 +105,7 @@ static int launch_conv(const void* in, const ConvW& w, const void* resid, void* 
     // layers 2-4: 256-pixel x 128-channel tiles (each wave 128 px x 64 ch: 0.75 LDS reads per MFMA, half the weight DMA per FLOP)
     static_assert(COUT % 128 == 0, "the halo16 kernel takes 128-channel tiles");
     constexpr int BM = 256, BN = 128;
-    using L = Halo16Lds<WI, BM, BN>;
+    using L = Halo16Lds<WI, BM, BN, COUT>;
     constexpr auto kern = conv3x3_halo16_kernel<T, CIN, COUT, HI, WI, BM, BN, L::NSW, RELU, RESID, OUTF32, 0, POOL>;
     const TileGrid g = tile_grid(M, BM, COUT / BN, HIPAC_HALO_GRID);
     return launch_dyn_lds<kern>(g.blocks, 256, L::LDS, s, (const T*)in, (const T*)w.w, w.bias, (const T*)resid, out, M, n, g.n_mtiles,
@@ -129,7 +126,7 @@ template <typename T, int CO, int HO, int PCIN>
 static int launch_conv_projk(const void* tmp, const ConvW& w2, const ConvW& wp, const float* bias_sum, const void* xblk, void* out,
                              int n, hipStream_t s, const char* zero_page) {
   constexpr int BM = 256, BN = 128;
-  using L = Halo16Lds<HO, BM, BN>;
+  using L = Halo16Lds<HO, BM, BN, CO>;
   constexpr auto kern = conv3x3_halo16_kernel<T, CO, CO, HO, HO, BM, BN, L::NSW, true, false, false, PCIN>;
   const int M = n * HO * HO;
   const TileGrid g = tile_grid(M, BM, CO / BN, HIPAC_HALO_GRID);
@@ -218,7 +215,7 @@ template <int CIN, int COUT, int HW, bool RELU, bool RESID, bool Q8OUT, bool POO
 static int launch_halo16x2(const void* in, const void* in_q, const ConvW& w, const void* resid, void* out, void* out_q, int n, hipStream_t s,
                            const void* resid_q = nullptr, const void* wgt_p = nullptr, const float* bias = nullptr) {
   constexpr int BM = 256, BN = COUT % 128 == 0 ? 128 : 64;
-  constexpr int LDS = halo_band_pieces(HW, BM) * 1024 + (BN == 64 ? HIPAC_Q8_NSW64 : 2) * BN * 128;
+  constexpr int LDS = halo16x2_lds_bytes(HW, BN, COUT);
   constexpr auto kern = conv3x3_halo16x2_kernel<CIN, COUT, HW, HW, BN, RELU, RESID, Q8OUT, POOL, OUTF32, S2, PCIN, LO16, X3>;
   const int M = n * HW * HW;
   const TileGrid g = tile_grid(M, BM, COUT / BN, HIPAC_HALO_GRID);

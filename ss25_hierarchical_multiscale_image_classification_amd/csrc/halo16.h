@@ -73,6 +73,12 @@ __device__ __forceinline__ void lds_read16(F& f, unsigned addr) {
   static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(addr), "n"(OFF));
 }
+// behind the wait for an lds_read16 whose value ordinary code (not another asm statement) goes on to read: the value is
+// "made" here, so that code cannot be moved in front of the wait
+template <typename F>
+__device__ __forceinline__ void asm_landed(F& f) {
+  asm volatile("" : "+v"(f));
+}
 #if defined(__HIP_DEVICE_COMPILE__)
 // rows = 16 lanes: a.row1 <-> b.row0, a.row3 <-> b.row2 (tools/permswap16_probe.hip)
 __device__ __forceinline__ void permlane16_swap(unsigned& a, unsigned& b) {
@@ -121,6 +127,17 @@ __host__ __device__ constexpr int perm16_inv(int j) { return (j & 1) ? (j + 7) /
 // walk leaves its image: no atomics, one fixed order, so the features are reproducible bit for bit.  resnet_head.hip's
 // head_pool_kernel adds the <= 2 x WM partial sums of an image in a fixed order, divides by H*W and applies the fc.
 constexpr int kPoolSlots = 7;  // images a 256-pixel tile of 49-pixel maps can meet (1 + 5 x 49 + 10)
+
+// Dynamic LDS of conv3x3_halo16_kernel, for the kernel and its launchers: the band, then S_BYTES = the weight ring of NSW slots
+// (or 4 waves x [32 px][BN / 2 fp32 + pad], the size kept from a staged epilogue, if that is larger), then the layer's COUT
+// bias floats.  No DMA reaches the bias: band pieces and the projection gather stay inside the band region (the `band slots`
+// assert), the residual tile fills BM * 128 bytes of the band region and of S_BYTES.
+constexpr int halo16_s_bytes(int BN, int NSW) {
+  return NSW * BN * 128 > 4 * 32 * (BN / 2 * 4 + 16) ? NSW * BN * 128 : 4 * 32 * (BN / 2 * 4 + 16);
+}
+constexpr int halo16_lds_bytes(int W, int BM, int BN, int NSW, int COUT) {
+  return halo_band_pieces(W, BM) * 1024 + halo16_s_bytes(BN, NSW) + COUT * 4;
+}
 
 #if defined(__HIP_DEVICE_COMPILE__)
 template <int CTRL>
@@ -176,10 +193,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
   static_assert(NSW == 2 || NSW == 3, "weight ring depth");
   // LDS behind the band: the weight ring, or 4 waves x [32 px][WTN fp32 + pad] if that is larger (the size the launchers
   // reserve, kept from a staged epilogue)
-  constexpr int SROWW = WTN * 4 + 16;
-  constexpr int STG_BYTES = 4 * 32 * SROWW;
-  constexpr int S_BYTES = NSW * W_BYTES > STG_BYTES ? NSW * W_BYTES : STG_BYTES;
-  static_assert(A_BYTES + S_BYTES <= 80 * 1024, "LDS: two workgroups per CU");
+  constexpr int S_BYTES = halo16_s_bytes(BN, NSW);
+  static_assert(S_BYTES >= NSW * W_BYTES, "weight ring");
+  // behind both: the layer's bias, staged once per workgroup (Bl below)
+  static_assert(COUT * 4 <= 2048 && A_BYTES + S_BYTES + COUT * 4 == halo16_lds_bytes(W, BM, BN, NSW, COUT), "LDS layout");
+  static_assert(halo16_lds_bytes(W, BM, BN, NSW, COUT) <= 80 * 1024, "LDS: two workgroups per CU");
   // the last sub-tile's taps may read past the tile's own band (tail tiles are not clamped): still inside the band region
   static_assert(BM + 2 * W + 4 <= A_PIECES * 8, "band slots");
 
@@ -246,9 +264,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
     }
   };
 
+  // The layer's bias, once per workgroup.  The epilogue must not LOAD it: a vector load issued next to the next tile's
+  // prefetch makes hipcc put its own `s_waitcnt vmcnt` for the load behind the prefetch branch's join, where it has to assume
+  // the branch was not taken -- with the branch taken that wait drains the prefetch inside the epilogue, on every tile.
+  float* const Bl = reinterpret_cast<float*>(ring + A_BYTES + S_BYTES);
+  for (int c = tid; c < COUT; c += 256) Bl[c] = bias[c];
+  __syncthreads();
+
   // The next tile's band and first weights are requested BEFORE the epilogue's stores, and vector-memory operations
   // retire in order: at the next tile's first step it is enough to wait until only those stores are outstanding -- if every
-  // one of them was issued, i.e. the tile was full (a store whose lanes are all past M may be branched around)
+  // one of them was issued, i.e. the tile was full (a store whose lanes are all past M may be branched around).  Between that
+  // request and the last store hipcc must have no reason for a vmcnt wait of its own (tools/vmwaits.py lists them).
   constexpr int N_EPI_STORES = MT * (OUTF32 ? NT : NT / 2);
   bool prev_full = false;
   for (int vb = blockIdx.x, first_tile = 1;; vb += gridDim.x, first_tile = 0) {
@@ -522,9 +548,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
   // 16 contiguous bytes -- row g of the wave stores channels 32 jp + 16 (g & 1) + 8 (g >> 1) .. + 7 -- so one store
   // instruction writes 64 contiguous bytes per pixel (the 32x32 form of this idea gave 32-byte runs and lost to the
   // staged form).
-  float4 bv[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) bv[j] = *reinterpret_cast<const float4*>(bias + n0 + wn * WTN + 16 * j + 4 * g);
+  // the lane's bias values from Bl, through the K loop's asm form: a plain LDS read behind an LDS-DMA gets a compiler vmcnt(0)
+  f32x4 bv[NT];
+  static_for<NT>([&](auto J) {
+    lds_read16<decltype(J)::value * 64>(bv[decltype(J)::value], lds0 + (unsigned)(A_BYTES + S_BYTES + (n0 + wn * WTN + 4 * g) * 4));
+  });
   const int c_lane = n0 + wn * WTN + 16 * (g & 1) + 8 * (g >> 1);  // + 32 jp: first of the 8 channels this lane stores
   // STAGE16: the 16-byte items (one pixel each, neighbouring lanes on DIFFERENT pixels: every store instruction touches 16
   // half lines and costs the address coalescer 4x the cycles of a contiguous one -- removing the stores altogether made the
@@ -554,6 +582,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16_kernel(const T* __restr
     }
   }
   HALO_STAMP(t_pref);
+  wait_lgkmcnt<0>();  // bv has landed (asm volatile statements keep their order: its readers follow the empty ones)
+  static_for<NT>([&](auto J) { asm_landed(bv[decltype(J)::value]); });
 #if HIPAC_H16_EPI_PRIO
   __builtin_amdgcn_s_setprio(HIPAC_H16_EPI_PRIO);
 #endif

@@ -61,6 +61,11 @@ namespace hipac {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
+// dynamic LDS of conv3x3_halo16x2_kernel (256-pixel tiles), for the kernel and its launcher: band, weight ring, the layer's bias
+constexpr int halo16x2_lds_bytes(int W, int BN, int COUT) {
+  return halo_band_pieces(W, 256) * 1024 + (BN == 64 ? HIPAC_Q8_NSW64 : 2) * BN * 128 + COUT * 4;
+}
+
 // D += 2^(sa - 127) 2^(sb - 127) A B, A / B e4m3 (cbsz = blgp = 0), K = 128
 __device__ __forceinline__ void mfma_f8_scaled(f32x4& c, const i32x8& a, const i32x8& b, int sa, int sb) {
   asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(a), "v"(b), "v"(sa), "v"(sb));
@@ -158,7 +163,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
   static_assert(NSTEP > NSW, "K steps");
   constexpr int S_BYTES = NSW * W_BYTES;
   static_assert((BN == 64 || BN == 128) && CIN % 64 == 0 && COUT % BN == 0 && (MT == 8 || MT == 4) && NT == 4, "tile shape");
-  static_assert(A_BYTES + S_BYTES <= 80 * 1024, "LDS: two workgroups per CU");
+  // behind both: the layer's bias, staged once per workgroup (halo16.h, Bl); no DMA reaches it
+  static_assert(COUT * 4 <= 2048 && A_BYTES + S_BYTES + COUT * 4 == halo16x2_lds_bytes(W, BN, COUT), "LDS layout");
+  static_assert(halo16x2_lds_bytes(W, BN, COUT) <= 80 * 1024, "LDS: two workgroups per CU");
   static_assert(BM + 2 * W + 4 <= A_PIECES * 8, "band slots");
   static_assert(!POOL || (BN == 128 && RELU && !Q8OUT && !OUTF32 && (BM + H * W - 1) / (H * W) + 1 <= kPoolSlots && H * W > 16), "pooled epilogue");
   static_assert(!OUTF32 || !Q8OUT, "the fp32 map has no q8 tensor");
@@ -256,6 +263,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
       for (int k = 0; k < HIPAC_Q8_DEPHASE; ++k) __builtin_amdgcn_s_sleep(127);
     }
   }
+  // the layer's bias, once per workgroup: the epilogue reads it from LDS, not from memory (halo16.h, above N_EPI_STORES)
+  float* const Bl = reinterpret_cast<float*>(ring + A_BYTES + S_BYTES);
+  for (int c = tid; c < COUT; c += 256) Bl[c] = bias[c];
+  __syncthreads();
   constexpr int N_EPI_STORES = OUTF32 ? MT * NT : MT * (2 + (LO16 ? 2 : 0) + (Q8OUT ? 2 : 0));  // hi16, lo16 (two 32-channel halves each), hi8, lo8
   static_assert(LO16 || Q8OUT, "an output without lo plane and without q8 tensor is a plain fp16 map");
   static_assert(N_EPI_STORES < 64, "vmcnt range");
@@ -558,9 +569,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
   }
   // ---- epilogue (direct, halo16.h) ----------------------------------------------------------------
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");  // XDL write -> VALU read of the accumulators
-  float4 bv[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) bv[j] = *reinterpret_cast<const float4*>(bias + n0 + wn * WTN + 16 * j + 4 * g);
+  f32x4 bv[NT];  // from Bl, through the asm form (halo16.h)
+  static_for<NT>([&](auto J) {
+    lds_read16<decltype(J)::value * 64>(bv[decltype(J)::value], lds0 + (unsigned)(A_BYTES + S_BYTES + (n0 + wn * WTN + 4 * g) * 4));
+  });
   const int c_lane = n0 + wn * WTN + 16 * (g & 1) + 8 * (g >> 1);  // + 32 jp: first of the 8 channels of a 16-bit store
   __builtin_amdgcn_s_barrier();  // every wave has left the K loop: band and ring are free
   {
@@ -577,6 +589,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo16x2_kernel(const _Float16
       for (int ps = 0; ps < PRE; ++ps) issue_w(ps, ps);
     }
   }
+  wait_lgkmcnt<0>();  // bv has landed
+  static_for<NT>([&](auto J) { asm_landed(bv[decltype(J)::value]); });
   [[maybe_unused]] f32x4 poolS[NT][2];
   [[maybe_unused]] int pool_slot = 0, pool_bound = 0;
   [[maybe_unused]] auto pool_flush = [&](int slot_) {

@@ -311,7 +311,7 @@ constexpr int kStripSteps = 14;  // 56 pooled rows / 4 per step
 // Schedule: ONE 8-wave workgroup per CU holds two TEAMS of four waves (team = wave >> 2, i.e. the two
 // waves that share a SIMD belong to different teams).  A team works on its own strips with its own LDS;
 // its step is cut into two halves that alternate behind ONE workgroup barrier per half:
-//     H1(n): request the input rows of step n+1 (LDS-DMA) . the 96-MFMA loop of step n
+//     H1(n): the 96-MFMA loop of step n . request the input rows of step n+1 (LDS-DMA)
 //     H2(n): epilogue of step n (pooling in registers, store) . conversion of the rows of step n+1
 // and team B runs one half behind team A: whenever one wave of a SIMD is in its MFMA loop its partner is
 // in the VALU / LDS / store half -- matrix beside vector work, never matrix beside matrix.  Every wave
@@ -624,7 +624,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_strip2_kernel(const unsigned
             issue_dma(tg, 0);  // prologue: nothing was requested yet
             wait_vmcnt<0>();
           } else {
-            wait_vmcnt<Q8 ? 16 : SPLIT ? 8 : 4>();  // this wave's raw rows of step n+1 (requested at the end of H2(n-1)) are older than its 4 (8; Q8: 16) stores
+            wait_vmcnt<Q8 ? 16 : SPLIT ? 8 : 4>();  // this wave's raw rows of step n+1 (requested at the end of H1(n)) are older than its 4 (8; Q8: 16) stores
           }
           HALO_STAMP(z_tw);
 #ifdef HIPAC_ABL_STRIP_NO_CONVERT
@@ -636,16 +636,13 @@ __global__ __launch_bounds__(512, 2) void stem_pool_strip2_kernel(const unsigned
           HALO_STAMP(z_tc);
           if (n >= 0) z_sum[2] += z_tw - z_te, z_sum[3] += z_tc - z_tw;
 #endif
-          // the raw rows are consumed (this wave converts only rows it requested itself): request those of step n + 2
-          // now, a whole MFMA half ahead of their use -- issuing them at the start of H1 sat in front of the MFMAs
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef HIPAC_ABL_STRIP_NO_DMA
-          if (n_strips < 0)
-#endif
-          if (gn + 1 < n_steps) issue_dma(tg + ((gn + 1) / kStripSteps) * tstride, (gn + 1) % kStripSteps);
+          // (the raw rows are consumed -- this wave converts only rows it requested itself -- but those of step n + 2 are
+          // NOT requested here: hipcc puts a `s_waitcnt vmcnt(0)` in front of the first LDS read behind an LDS-DMA, and that read
+          // is H1's bias read, so H1 began by waiting out the round trip of rows nobody needs before H2.  H1 requests them
+          // itself, behind its last LDS read.)
         }
       } else {
-        // ---------------- H1(n): request the rows of step n + 1, MFMA loop of step n ----------------
+        // ---------------- H1(n): MFMA loop of step n, request the rows of step n + 1 ----------------
         f32x16 binit;
         {
           const int strip1 = tg + (n / kStripSteps) * tstride, ys1 = n % kStripSteps, side1 = strip1 & 1;
@@ -722,6 +719,13 @@ __global__ __launch_bounds__(512, 2) void stem_pool_strip2_kernel(const unsigned
             __builtin_amdgcn_sched_barrier(0);
           });
         }
+        // the rows of step n + 1, converted in H2(n) behind its epilogue: the round trip hides behind the pooling and the stores.
+        // Issued behind the MFMA loop's last LDS read (at the start of H1 the address arithmetic sat in front of the MFMAs, and
+        // the compiler's wait in front of the fragment reads); the raw rows' last reader was this wave's own convert in H2(n-1).
+#ifdef HIPAC_ABL_STRIP_NO_DMA
+        if (n_strips < 0)
+#endif
+        if (n + 1 < n_steps) issue_dma(tg + ((n + 1) / kStripSteps) * tstride, (n + 1) % kStripSteps);
 #if HIPAC_STRIP_PRIO == 1
         __builtin_amdgcn_s_setprio(0);
 #endif
