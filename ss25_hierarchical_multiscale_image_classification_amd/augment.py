@@ -18,7 +18,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import capi
+from . import augment_hed, capi
 from .transforms import RandomResizedCrop
 
 PARAMS = 24  # int32 per view (include/hipac.h, hipac_augment_views)
@@ -243,10 +243,12 @@ class DevicePatchPool:
                                    torch.empty((n_views, OUT, OUT, 3), dtype=torch.uint8, device=dev))}
         return self._scratch[key]
 
-    def augment(self, params: np.ndarray, want_u8: bool = False, want_float: bool = True, geometry: int = 0):
+    def augment(self, params: np.ndarray, want_u8: bool = False, want_float: bool = True, geometry: int = 0, hed=None):
         """params int32 [n_views, 24] (host) -> float32 [n_views, 3, 224, 224] on the device (and / or the uint8
         [n_views, 224, 224, 3] image before ToTensor).  ``geometry``: 0 = resized crop (SimCLR), 1 = flips + rotation
-        (the classifier loops' transform; 224-pixel patches)."""
+        (the classifier loops' transform; 224-pixel patches).  ``hed``: float64 [n_views, 12] (host), the views' HED stain maps
+        (``augment_hed.draw_maps``), applied between the geometry and the colour operations by ``hipac_augment_views_hed``;
+        None = no such stage, the ``hipac_augment_views`` call."""
         params = np.ascontiguousarray(params, dtype=np.int32)
         if params.ndim != 2 or params.shape[1] != PARAMS:
             raise capi.HipacError("augment: params must be int32 [n_views, 24]")
@@ -266,16 +268,44 @@ class DevicePatchPool:
         host.numpy()[:] = params
         out = torch.empty((n, 3, OUT, OUT), dtype=torch.float32, device=self.device) if want_float else None
         out_u8 = torch.empty((n, OUT, OUT, 3), dtype=torch.uint8, device=self.device) if want_u8 else None
-        lib = capi.load_library()
         with torch.cuda.device(self.device):
-            capi._check(lib.hipac_augment_views(self.patches.data_ptr(), self.n, self.P, int(geometry), host.data_ptr(), pdev.data_ptr(), n,
-                                                self.tab_bounds.data_ptr(), self.tab_kk.data_ptr(), self.ksize, self.lut.data_ptr(),
-                                                tmp.data_ptr(), crops.data_ptr(), out.data_ptr() if out is not None else None,
-                                                out_u8.data_ptr() if out_u8 is not None else None, capi._stream()),
-                        "hipac_augment_views")
+            if hed is None:
+                capi._check(capi.load_library().hipac_augment_views(
+                    self.patches.data_ptr(), self.n, self.P, int(geometry), host.data_ptr(), pdev.data_ptr(), n, self.tab_bounds.data_ptr(),
+                    self.tab_kk.data_ptr(), self.ksize, self.lut.data_ptr(), tmp.data_ptr(), crops.data_ptr(),
+                    out.data_ptr() if out is not None else None, out_u8.data_ptr() if out_u8 is not None else None, capi._stream()),
+                    "hipac_augment_views")
+            else:
+                self._augment_hed(hed, int(geometry), host, pdev, n, tmp, crops, out, out_u8)
             evs[slot] = torch.cuda.Event()
             evs[slot].record(torch.cuda.current_stream(self.device))
         return (out, out_u8) if want_u8 else out
+
+    def _augment_hed(self, hed, geometry: int, host, pdev, n: int, tmp, crops, out, out_u8):
+        """``augment``'s enqueue with HED maps (called with the pool's device current): the payload goes through a pinned ring of
+        its own, as the parameters do."""
+        maps = augment_hed.check_maps(hed, n)
+        ring = self.__dict__.setdefault("_hed_pin", augment_hed.PinnedRing())
+        slot, hhost = ring.stage(maps)
+        hdev = self.__dict__.get("_hed_dev")
+        if hdev is None or hdev.shape[0] < n:
+            hdev = self._hed_dev = torch.empty((n, augment_hed.PAYLOAD), dtype=torch.float64, device=self.device)
+        capi._check(augment_hed.load_augment_hed_library().hipac_augment_views_hed(
+            self.patches.data_ptr(), self.n, self.P, geometry, host.data_ptr(), pdev.data_ptr(), n, self.tab_bounds.data_ptr(),
+            self.tab_kk.data_ptr(), self.ksize, self.lut.data_ptr(), tmp.data_ptr(), crops.data_ptr(),
+            out.data_ptr() if out is not None else None, out_u8.data_ptr() if out_u8 is not None else None, hhost.data_ptr(),
+            hdev.data_ptr(), capi._stream()), "hipac_augment_views_hed")
+        ring.mark(slot, self.device)
+
+
+def _hed_setup(hed_sigma: float, seed: int, rank: int):
+    """(sigma, the generator of the HED draws or None for sigma 0); ValueError for a sigma outside 0 .. 0.5."""
+    sigma = augment_hed.check_sigma(hed_sigma)
+    return sigma, (augment_hed.hed_rng(seed, rank) if sigma > 0.0 else None)
+
+
+def _hed_draw(n_views: int, sigma: float, rng):
+    return None if rng is None else augment_hed.draw_maps(n_views, sigma, rng)
 
 
 class DeviceSimCLRLoader:
@@ -284,13 +314,17 @@ class DeviceSimCLRLoader:
     (src/models/simclr.py:70-73).  ``indices_of(epoch)`` may be overridden by a sampler (rank shares)."""
 
     def __init__(self, pool: DevicePatchPool, batch_size: int, shuffle: bool = True, seed: int = 0, rank: int = 0, world: int = 1,
-                 drop_last: bool = False, mirror_host_draws: bool = False):
+                 drop_last: bool = False, mirror_host_draws: bool = False, hed_sigma: float = 0.0, hed_seed: Optional[int] = None):
         """``mirror_host_draws``: take every view's parameters with ``draw_simclr_view`` from torch's / random's global
-        generators (the host transforms' own draw order; tests), instead of the batched numpy draws."""
+        generators (the host transforms' own draw order; tests), instead of the batched numpy draws.  ``hed_sigma`` > 0
+        (additive, ``--aug_hed``): every view i and every view j also gets a HED stain map of its own (``augment_hed``), drawn
+        from a generator of its own, ``default_rng([hed_seed, rank, 11])`` (``hed_seed`` None = ``seed``); 0 builds no maps and takes
+        the call without them."""
         self.pool, self.batch_size, self.shuffle, self.seed = pool, int(batch_size), shuffle, seed
         self.rank, self.world, self.drop_last, self.epoch = rank, world, drop_last, 0
         self.mirror_host_draws = mirror_host_draws
         self._rng = np.random.default_rng([seed, rank])
+        self.hed_sigma, self._hed_rng = _hed_setup(hed_sigma, seed if hed_seed is None else hed_seed, rank)
 
     def __len__(self):
         n = len(self.pool)
@@ -324,7 +358,8 @@ class DeviceSimCLRLoader:
                     rows[1, k] = draw_simclr_view(idx, P, P)
             else:
                 rows[0], rows[1] = draw_simclr_batch(b, P, self._rng), draw_simclr_batch(b, P, self._rng)
-            x = self.pool.augment(rows.reshape(-1, PARAMS))
+            hed = _hed_draw(2 * len(b), self.hed_sigma, self._hed_rng)  # view i of every sample, then view j: the rows' order
+            x = self.pool.augment(rows.reshape(-1, PARAMS), hed=hed)
             yield x[:len(b)], x[len(b):]
         self.epoch += 1
 
@@ -336,7 +371,10 @@ class DeviceClassifierLoader:
     transform (validation)."""
 
     def __init__(self, pool: DevicePatchPool, batch_size: int, shuffle: bool = True, augment: bool = True, seed: int = 0, rank: int = 0,
-                 world: int = 1, indices: Optional[Sequence[int]] = None):
+                 world: int = 1, indices: Optional[Sequence[int]] = None, hed_sigma: float = 0.0, hed_seed: Optional[int] = None):
+        """``hed_sigma`` > 0 (additive, ``--aug_hed``; training loaders only): EVERY patch of a batch, normal or tumour, gets a HED
+        stain map -- a stain shift that only the tumour patches received (as ``train_transform`` does with its flips and jitter)
+        would itself become the label.  The draws come from ``default_rng([hed_seed, rank, 11])`` (``hed_seed`` None = ``seed``)."""
         if pool.P != OUT:
             raise capi.HipacError("DeviceClassifierLoader: the flips / rotation / jitter act on 224-pixel patches (level 3); "
                                   "other levels keep the host transforms")
@@ -346,6 +384,9 @@ class DeviceClassifierLoader:
         self.seed, self.rank, self.world, self.epoch = seed, rank, world, 0
         self.indices = list(range(len(pool))) if indices is None else [int(i) for i in indices]
         self._rng = np.random.default_rng([seed, rank, 7])
+        self.hed_sigma, self._hed_rng = _hed_setup(hed_sigma, seed if hed_seed is None else hed_seed, rank)
+        if self.hed_sigma > 0.0 and not augment:
+            raise capi.HipacError("DeviceClassifierLoader: hed_sigma is for training loaders (augment=True); validation is not augmented")
 
     def __len__(self):
         return math.ceil(len(self.indices) / self.batch_size)
@@ -372,7 +413,8 @@ class DeviceClassifierLoader:
                 continue
             labels = [self.pool.labels[j] for j in b]
             rows = draw_train_batch(b, [self.augment and lab == 1 for lab in labels], self._rng)
-            yield self.pool.augment(rows, geometry=1), torch.tensor(labels, dtype=torch.int64), b
+            hed = _hed_draw(len(b), self.hed_sigma, self._hed_rng)
+            yield self.pool.augment(rows, geometry=1, hed=hed), torch.tensor(labels, dtype=torch.int64), b
         self.epoch += 1
 
 

@@ -33,7 +33,7 @@ PUBLIC_HEADERS = [PKG.parent / "include" / "hipac.h", PKG.parent / "include" / "
                   PKG.parent / "include" / "hipac_mil_dropout.h", PKG.parent / "include" / "hipac_mil_heads.h",
                   PKG.parent / "include" / "hipac_mil_gated.h", PKG.parent / "include" / "hipac_mil_levels.h",
                   PKG.parent / "include" / "hipac_validate.h", PKG.parent / "include" / "hipac_eval_ci.h",
-                  PKG.parent / "include" / "hipac_pair_tap.h"]
+                  PKG.parent / "include" / "hipac_pair_tap.h", PKG.parent / "include" / "hipac_augment_hed.h"]
 ARCH = "gfx950"
 # -ffp-contract=off: the host-side Pillow coefficient restatement must round every
 # double operation separately (no fused multiply-add), see preprocess.hip.

@@ -22,6 +22,9 @@
 // step needs a whole-image mean between two of them).  Bound: HBM (0.6 MB written per view); 2 x 1024 views take ~0.2 ms.
 #include "common.h"
 
+#include "../../include/hipac_augment_hed.h"
+#include "augment_hed.h"
+
 // Pillow's C is compiled without fused multiply-add: every product below is rounded before it is added
 #pragma clang fp contract(off)
 
@@ -29,6 +32,9 @@ namespace hipac {
 
 constexpr int kAugParams = 24;  // int32 per view, see include/hipac.h
 constexpr int kOut = 224;
+static_assert(kHedPayload == HIPAC_AUGMENT_HED_PAYLOAD, "payload layout of include/hipac_augment_hed.h");
+
+__constant__ int32_t kAugOd[256] = {HIPAC_STAIN_OD_LIST};  // this translation unit's copy of stain.hip's table (one literal: stain_od.h)
 
 __device__ __forceinline__ int clip8i(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
@@ -158,16 +164,36 @@ __device__ __forceinline__ void hsv2rgb8(int h, int s, int v, int& r, int& g, in
 
 // colour operations of one view in LDS, then ToTensor / Normalize.  ops[4]: 0 brightness, 1 contrast, 2 saturation, 3 hue,
 // -1 none, applied in this order; out: float [view][3][224][224]
+//
+// kHed: the HED stain augmentation of include/hipac_augment_hed.h, applied while the view is loaded into LDS (after the geometric
+// stage, before the colour operations): hed = double[view][12], and 4.8 KB more LDS for od[] as double and the inverse's buckets (augment_hed.h)
 constexpr int kColorThreads = 1024;  // one workgroup per CU (LDS): 16 waves hide the hue step's fp64 latency
+constexpr int kColorLds = kOut * kOut * 3 + kColorThreads / 64 * 4;
+static_assert(kColorLds % 8 == 0 && kColorLds + kHedTableBytes <= 160 * 1024, "the view, the partial sums and the OD tables share one CU's LDS");
+template <bool kHed>
 __global__ __launch_bounds__(kColorThreads) void aug_color_kernel(const unsigned char* __restrict__ img, const int* __restrict__ params,
                                                         const float* __restrict__ lut, float* __restrict__ out,
-                                                        unsigned char* __restrict__ out_u8) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char px[];  // [224*224][3] then int red[4]
+                                                        unsigned char* __restrict__ out_u8, const double* __restrict__ hed) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char px[];  // [224*224][3], int red[16], then (kHed) double odf[256], uint16 inv16[1420]
   constexpr int NPX = kOut * kOut;
   int* red = reinterpret_cast<int*>(px + NPX * 3);  // [kColorThreads / 64]
   const int v = blockIdx.x, tid = threadIdx.x;
   const int* pr = params + v * kAugParams;
-  {
+  if constexpr (kHed) {
+    double* odf = reinterpret_cast<double*>(px + kColorLds);
+    uint16_t* inv16 = reinterpret_cast<uint16_t*>(odf + 256);
+    hed_build_tables(kAugOd, odf, inv16, tid, kColorThreads);
+    double m[kHedPayload];
+#pragma unroll
+    for (int i = 0; i < kHedPayload; ++i) m[i] = hed[(size_t)v * kHedPayload + i];
+    const unsigned* src = reinterpret_cast<const unsigned*>(img + (size_t)v * NPX * 3);
+    unsigned* dst = reinterpret_cast<unsigned*>(px);
+    for (int g = tid; g < NPX / 4; g += kColorThreads) {  // four pixels = three dwords
+      unsigned w0 = src[3 * g], w1 = src[3 * g + 1], w2 = src[3 * g + 2];
+      hed_group(odf, inv16, m, w0, w1, w2);
+      dst[3 * g] = w0, dst[3 * g + 1] = w1, dst[3 * g + 2] = w2;
+    }
+  } else {
     const unsigned* src = reinterpret_cast<const unsigned*>(img + (size_t)v * NPX * 3);  // 150528 bytes = 37632 dwords
     unsigned* dst = reinterpret_cast<unsigned*>(px);
     for (int i = tid; i < NPX * 3 / 4; i += kColorThreads) dst[i] = src[i];
@@ -236,21 +262,42 @@ __global__ __launch_bounds__(kColorThreads) void aug_color_kernel(const unsigned
   }
 }
 
-}  // namespace hipac
+// the HED stage alone, in place: view blockIdx.y, four pixels (three dwords) per thread
+constexpr int kHedApplyBlocks = kOut * kOut / 4 / 256;  // 49 workgroups of 256 threads per view
+static_assert(kHedApplyBlocks * 256 * 4 == kOut * kOut, "a view is a whole number of workgroups");
+__global__ __launch_bounds__(256) void aug_hed_apply_kernel(unsigned char* __restrict__ images, const double* __restrict__ hed) {
+  __shared__ double odf[256];
+  __shared__ uint16_t inv16[kHedBuckets];
+  const int v = blockIdx.y;
+  hed_build_tables(kAugOd, odf, inv16, threadIdx.x, 256);
+  double m[kHedPayload];
+#pragma unroll
+  for (int i = 0; i < kHedPayload; ++i) m[i] = hed[(size_t)v * kHedPayload + i];
+  unsigned* w = reinterpret_cast<unsigned*>(images + (size_t)v * kOut * kOut * 3) + 3 * (blockIdx.x * 256 + threadIdx.x);
+  unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+  hed_group(odf, inv16, m, w0, w1, w2);
+  w[0] = w0, w[1] = w1, w[2] = w2;
+}
 
-using namespace hipac;
+// 0 or HIPAC_EINVAL with the message set; hed_host: HOST double[n_views][12]
+static int hed_check_payload(const char* who, const double* hed_host, int n_views) {
+  for (size_t i = 0; i < (size_t)n_views * kHedPayload; ++i)
+    HIPAC_REQUIRE(hed_host[i] - hed_host[i] == 0.0, HIPAC_EINVAL, "%s: view %zu: payload entry %zu is not finite", who, i / kHedPayload,
+                  i % kHedPayload);
+  return 0;
+}
 
-extern "C" {
-
-int hipac_augment_views(const uint8_t* pool, int64_t n_pool, int P, int geometry, const int32_t* params_host, int32_t* params_dev,
-                        int n_views, const int32_t* tab_bounds, const int32_t* tab_kk, int ksize, const float* lut, uint8_t* tmp,
-                        uint8_t* crops, float* out, uint8_t* out_u8, void* stream) {
-  HIPAC_REQUIRE(pool && params_host && params_dev && lut && crops && (out || out_u8), HIPAC_EINVAL, "augment_views: null argument");
-  HIPAC_REQUIRE(geometry == 0 || geometry == 1, HIPAC_EINVAL, "augment_views: geometry %d (0: resized crop, 1: flips + rotation)", geometry);
-  HIPAC_REQUIRE(geometry == 1 || (tab_bounds && tab_kk && tmp && ksize >= 1), HIPAC_EINVAL, "augment_views: the resized crop needs its tables");
-  HIPAC_REQUIRE(geometry == 0 || P == kOut, HIPAC_EINVAL, "augment_views: flips + rotation act on 224-pixel patches (P = %d)", P);
-  HIPAC_REQUIRE(n_pool > 0 && P >= 1 && P <= 4096 && n_views > 0 && n_views <= 65535, HIPAC_EINVAL,
-                "augment_views: bad size (P %d, views %d)", P, n_views);
+// hipac_augment_views, with the HED stage in the colour kernel's load when hed_host is given
+static int augment_views_impl(const char* who, const uint8_t* pool, int64_t n_pool, int P, int geometry, const int32_t* params_host,
+                              int32_t* params_dev, int n_views, const int32_t* tab_bounds, const int32_t* tab_kk, int ksize,
+                              const float* lut, uint8_t* tmp, uint8_t* crops, float* out, uint8_t* out_u8, const double* hed_host,
+                              double* hed_dev, void* stream) {
+  HIPAC_REQUIRE(pool && params_host && params_dev && lut && crops && (out || out_u8), HIPAC_EINVAL, "%s: null argument", who);
+  HIPAC_REQUIRE(geometry == 0 || geometry == 1, HIPAC_EINVAL, "%s: geometry %d (0: resized crop, 1: flips + rotation)", who, geometry);
+  HIPAC_REQUIRE(geometry == 1 || (tab_bounds && tab_kk && tmp && ksize >= 1), HIPAC_EINVAL, "%s: the resized crop needs its tables", who);
+  HIPAC_REQUIRE(geometry == 0 || P == kOut, HIPAC_EINVAL, "%s: flips + rotation act on 224-pixel patches (P = %d)", who, P);
+  HIPAC_REQUIRE(n_pool > 0 && P >= 1 && P <= 4096 && n_views > 0 && n_views <= 65535, HIPAC_EINVAL, "%s: bad size (P %d, views %d)", who,
+                P, n_views);
   // the kernels index the pool with these numbers: check them where they are still host memory
   for (int v = 0; v < n_views; ++v) {
     const int32_t* pr = params_host + (size_t)v * kAugParams;
@@ -264,12 +311,17 @@ int hipac_augment_views(const uint8_t* pool, int64_t n_pool, int P, int geometry
     bool fix_ok = true;
     if (geometry == 1)
       for (int k = 17; k <= 22; ++k) fix_ok = fix_ok && pr[k] > -(1 << 26) && pr[k] < (1 << 26);
-    HIPAC_REQUIRE(crop_ok && ops_ok && fix_ok, HIPAC_EINVAL,
-                  "augment_views: view %d: source %d, crop (%d, %d, %d, %d) of a %d-pixel patch, ops %d %d %d %d", v, pr[0], pr[1],
-                  pr[2], pr[3], pr[4], P, pr[6], pr[7], pr[8], pr[9]);
+    HIPAC_REQUIRE(crop_ok && ops_ok && fix_ok, HIPAC_EINVAL, "%s: view %d: source %d, crop (%d, %d, %d, %d) of a %d-pixel patch, ops %d %d %d %d",
+                  who, v, pr[0], pr[1], pr[2], pr[3], pr[4], P, pr[6], pr[7], pr[8], pr[9]);
+  }
+  if (hed_host) {
+    HIPAC_REQUIRE(hed_dev, HIPAC_EINVAL, "%s: null argument (a payload needs its device scratch)", who);
+    if (int rc = hed_check_payload(who, hed_host, n_views)) return rc;
   }
   hipStream_t s = (hipStream_t)stream;
   HIPAC_CHECK_HIP(hipMemcpyAsync(params_dev, params_host, (size_t)n_views * kAugParams * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (hed_host)
+    HIPAC_CHECK_HIP(hipMemcpyAsync(hed_dev, hed_host, (size_t)n_views * kHedPayload * sizeof(double), hipMemcpyHostToDevice, s));
   const int32_t* params = params_dev;
   dim3 gv((kOut * kOut + 255) / 256, (unsigned)n_views);
   if (geometry == 0) {
@@ -279,18 +331,57 @@ int hipac_augment_views(const uint8_t* pool, int64_t n_pool, int P, int geometry
   } else {
     hipLaunchKernelGGL(aug_affine_kernel, gv, dim3(256), 0, s, pool, params, crops);
   }
-  constexpr int LDS = kOut * kOut * 3 + kColorThreads / 64 * 4;
   static bool attr_done[64] = {};
   {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
     if (dev < 0 || !attr_done[dev]) {
-      HIPAC_CHECK_HIP(hipFuncSetAttribute((const void*)aug_color_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+      HIPAC_CHECK_HIP(hipFuncSetAttribute((const void*)aug_color_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kColorLds));
+      HIPAC_CHECK_HIP(hipFuncSetAttribute((const void*)aug_color_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          kColorLds + kHedTableBytes));
       if (dev >= 0) attr_done[dev] = true;
     }
   }
-  hipLaunchKernelGGL(aug_color_kernel, dim3((unsigned)n_views), dim3(kColorThreads), LDS, s, (const unsigned char*)crops, params, lut, out,
-                     out_u8);
+  if (hed_host)
+    hipLaunchKernelGGL(aug_color_kernel<true>, dim3((unsigned)n_views), dim3(kColorThreads), kColorLds + kHedTableBytes, s,
+                       (const unsigned char*)crops, params, lut, out, out_u8, (const double*)hed_dev);
+  else
+    hipLaunchKernelGGL(aug_color_kernel<false>, dim3((unsigned)n_views), dim3(kColorThreads), kColorLds, s, (const unsigned char*)crops, params,
+                       lut, out, out_u8, (const double*)nullptr);
+  HIPAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace hipac
+
+using namespace hipac;
+
+extern "C" {
+
+int hipac_augment_views(const uint8_t* pool, int64_t n_pool, int P, int geometry, const int32_t* params_host, int32_t* params_dev,
+                        int n_views, const int32_t* tab_bounds, const int32_t* tab_kk, int ksize, const float* lut, uint8_t* tmp,
+                        uint8_t* crops, float* out, uint8_t* out_u8, void* stream) {
+  return augment_views_impl("augment_views", pool, n_pool, P, geometry, params_host, params_dev, n_views, tab_bounds, tab_kk, ksize, lut, tmp,
+                            crops, out, out_u8, nullptr, nullptr, stream);
+}
+
+int hipac_augment_hed_abi_version(void) { return HIPAC_AUGMENT_HED_ABI_VERSION; }
+
+int hipac_augment_views_hed(const uint8_t* pool, int64_t n_pool, int P, int geometry, const int32_t* params_host, int32_t* params_dev,
+                            int n_views, const int32_t* tab_bounds, const int32_t* tab_kk, int ksize, const float* lut, uint8_t* tmp,
+                            uint8_t* crops, float* out, uint8_t* out_u8, const double* hed_host, double* hed_dev, void* stream) {
+  return augment_views_impl(hed_host ? "augment_views_hed" : "augment_views", pool, n_pool, P, geometry, params_host, params_dev, n_views,
+                            tab_bounds, tab_kk, ksize, lut, tmp, crops, out, out_u8, hed_host, hed_dev, stream);
+}
+
+int hipac_augment_hed_apply(uint8_t* images, int n_views, const double* hed_host, double* hed_dev, void* stream) {
+  HIPAC_REQUIRE(images && hed_host && hed_dev, HIPAC_EINVAL, "augment_hed_apply: null argument");
+  HIPAC_REQUIRE(n_views >= 1 && n_views <= 65535, HIPAC_EINVAL, "augment_hed_apply: n_views %d outside 1..65535", n_views);
+  HIPAC_REQUIRE(((uintptr_t)images & 3) == 0, HIPAC_EINVAL, "augment_hed_apply: images not 4-byte aligned");
+  if (int rc = hed_check_payload("augment_hed_apply", hed_host, n_views)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPAC_CHECK_HIP(hipMemcpyAsync(hed_dev, hed_host, (size_t)n_views * kHedPayload * sizeof(double), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(aug_hed_apply_kernel, dim3(kHedApplyBlocks, (unsigned)n_views), dim3(256), 0, s, images, (const double*)hed_dev);
   HIPAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -16,24 +16,7 @@
 #include "common.h"
 
 #include "../../include/hipac_stain.h"
-
-#define HIPAC_STAIN_OD_LIST \
-  22713, 19874, 18213, 17035, 16121, 15374, 14743, 14196, 13713, 13282, 12891, 12535, 12207, 11903, 11621, 11357, \
-  11108, 10874, 10653, 10443, 10243, 10052, 9870, 9696, 9529, 9368, 9213, 9064, 8921, 8782, 8647, 8517, \
-  8391, 8269, 8150, 8035, 7923, 7813, 7707, 7603, 7502, 7404, 7307, 7213, 7121, 7031, 6943, 6857, \
-  6772, 6689, 6608, 6529, 6451, 6374, 6299, 6225, 6153, 6081, 6011, 5943, 5875, 5808, 5743, 5678, \
-  5615, 5552, 5491, 5430, 5370, 5311, 5253, 5196, 5139, 5084, 5029, 4974, 4921, 4868, 4816, 4764, \
-  4713, 4663, 4613, 4564, 4516, 4468, 4421, 4374, 4328, 4282, 4237, 4192, 4148, 4104, 4060, 4017, \
-  3975, 3933, 3891, 3850, 3810, 3769, 3729, 3690, 3650, 3612, 3573, 3535, 3497, 3460, 3423, 3386, \
-  3350, 3314, 3278, 3242, 3207, 3172, 3138, 3103, 3069, 3036, 3002, 2969, 2936, 2904, 2871, 2839, \
-  2807, 2776, 2744, 2713, 2682, 2651, 2621, 2591, 2561, 2531, 2501, 2472, 2443, 2414, 2385, 2357, \
-  2328, 2300, 2272, 2244, 2217, 2189, 2162, 2135, 2108, 2082, 2055, 2029, 2003, 1977, 1951, 1925, \
-  1900, 1874, 1849, 1824, 1799, 1774, 1750, 1725, 1701, 1677, 1653, 1629, 1605, 1582, 1558, 1535, \
-  1512, 1488, 1466, 1443, 1420, 1397, 1375, 1353, 1330, 1308, 1286, 1265, 1243, 1221, 1200, 1178, \
-  1157, 1136, 1115, 1094, 1073, 1052, 1032, 1011, 991, 970, 950, 930, 910, 890, 870, 850, \
-  831, 811, 792, 772, 753, 734, 715, 696, 677, 658, 639, 621, 602, 584, 565, 547, \
-  529, 511, 492, 474, 457, 439, 421, 403, 386, 368, 351, 333, 316, 299, 281, 264, \
-  247, 230, 213, 197, 180, 163, 147, 130, 114, 97, 81, 65, 48, 32, 16, 0
+#include "stain_od.h"
 
 namespace hipac {
 

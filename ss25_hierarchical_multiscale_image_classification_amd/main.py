@@ -40,6 +40,12 @@ every level is mapped in place to the usual Macenko target, or to the ``HE`` / `
 slide route and ``--detect``.  The Otsu mask is made from the original pixels and is not recomputed; the ``white`` rule
 (``mean > 240``) sees the normalised pixels.  Default ``none``: no byte of any output changes.
 
+``--aug_hed SIGMA`` is the training side of the same problem (``augment_hed.py``): under ``--device_aug`` / ``--from_slides`` every
+training view of ``--train`` / ``--train_strategy`` (both SimCLR views of ``self_supervised`` too; normal and tumour patches alike)
+gets a random HED stain map of its own in optical-density space, alpha ~ U(1 - SIGMA, 1 + SIGMA) and beta ~ U(-SIGMA, SIGMA) per
+stain, inside the colour kernel.  Keyed by ``--seed``; validation is never augmented; refused without the device pipeline.
+Default 0: no byte of any output and no call path changes.
+
 ``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by ``--detect``, or by
 ``features.save_froc_csv`` with one line per window) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
@@ -97,6 +103,25 @@ def _eval_ci(text: str) -> float:
     if not 0.0 < v < 100.0:
         raise argparse.ArgumentTypeError(f"takes a percentage above 0 and below 100, got {text}")
     return v
+
+
+def _aug_hed(text: str) -> float:
+    from .augment_hed import check_sigma
+
+    try:
+        return check_sigma(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def check_aug_args(parser, args):
+    """--aug_hed without the device input pipeline is refused as an argparse error (exit status 2): the host transforms have no
+    HED stage, and a flag that is dropped silently would be worse than none."""
+    if args.aug_hed > 0.0:
+        if not (args.train or args.train_strategy):
+            parser.error(f"--aug_hed {args.aug_hed:g} is an option of --train / --train_strategy")
+        if not (args.device_aug or args.from_slides):
+            parser.error(f"--aug_hed {args.aug_hed:g} needs the device input pipeline: give --device_aug or --from_slides")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -161,6 +186,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--from_slides", action="store_true",
                    help="--train / --train_strategy: no PNG tree -- the kept windows go from the slides in HBM straight into the "
                         "training pool (implies the device input pipeline)")
+    p.add_argument("--aug_hed", type=_aug_hed, default=0.0, metavar="SIGMA",
+                   help="training loops with --device_aug / --from_slides: HED stain augmentation of every training view on the "
+                        "device, alpha ~ U(1 - SIGMA, 1 + SIGMA) and beta ~ U(-SIGMA, SIGMA) per stain (0 = off, at most 0.5; "
+                        "0.05 light, 0.2 strong); the draws are keyed by --seed")
     p.add_argument("--simclr_precision", choices=["fp16", "fp32"], default="fp32",
                    help="arithmetic of the SimCLR pre-training step (the reference's loop is fp32, src/models/simclr.py:85-96)")
     p.add_argument("--train_mil", action="store_true",
@@ -465,20 +494,31 @@ def cmd_train(args, strategy: Optional[str]):
 
     level = int(args.patch_level) if args.patch_level != "all" else 3
     patch_dir = os.path.join(data_root(args), "patches", f"level_{level}")
+    hed = dict(hed_sigma=args.aug_hed, hed_seed=0 if args.seed is None else args.seed)
+    if args.aug_hed > 0.0 and int(os.environ.get("RANK", "0")) == 0:
+        from .augment_hed import describe
+
+        print(f"[INFO] {describe(args.aug_hed)}", flush=True)
     if args.from_slides:
         # every rank holds every slide: batches are shared out, not slides (an unreadable file is skipped on every rank alike)
         slides = [s for s in (try_open(name, make) for name, make in list_slides(args)) if s is not None]
         train_resnet_classifier(None, strategy=strategy, epochs=args.epochs, batch_size=args.batch_size, precision=args.precision,
                                 simclr_epochs=args.simclr_epochs, max_steps=args.max_steps, train_precision=args.train_precision,
-                                simclr_precision=args.simclr_precision, slides=slides, level=level)
+                                simclr_precision=args.simclr_precision, slides=slides, level=level, **hed)
         return 0
     if not (os.path.isdir(patch_dir) and os.listdir(patch_dir)):
         print("[ERROR] Patches must be extracted before training.")
         return 1
-    train_resnet_classifier(patch_dir, strategy=strategy, epochs=args.epochs, batch_size=args.batch_size,
-                            precision=args.precision, simclr_epochs=args.simclr_epochs, max_steps=args.max_steps,
-                            train_precision=args.train_precision, simclr_precision=args.simclr_precision,
-                            device_aug=args.device_aug)
+    try:
+        train_resnet_classifier(patch_dir, strategy=strategy, epochs=args.epochs, batch_size=args.batch_size,
+                                precision=args.precision, simclr_epochs=args.simclr_epochs, max_steps=args.max_steps,
+                                train_precision=args.train_precision, simclr_precision=args.simclr_precision,
+                                device_aug=args.device_aug, **hed)
+    except ValueError as e:
+        if args.aug_hed > 0.0 and str(e).startswith("hed_sigma"):  # e.g. --device_aug fell back to the host transforms
+            print(f"[ERROR] --aug_hed: {e}")
+            return 2
+        raise
     return 0
 
 
@@ -744,6 +784,7 @@ def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
     check_mil_args(parser, args)
+    check_aug_args(parser, args)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")

@@ -91,7 +91,8 @@ def get_simclr_transform():
 
 def pretrain_simclr(patch_dir: str, epochs: int = 200, batch_size: int = 512, lr: float = 1e-3, device: str = "cuda",
                     num_workers: int = 8, out_dir: str = ".", max_steps: Optional[int] = None, verbose: bool = True,
-                    final_path: Optional[str] = None, precision: str = "fp32", device_aug: bool = False, pool=None):
+                    final_path: Optional[str] = None, precision: str = "fp32", device_aug: bool = False, pool=None,
+                    hed_sigma: float = 0.0, hed_seed: int = 0):
     """src/models/simclr.py:68-124 with the step on the native kernels: PatchDataset(transform=None) ->
     SimCLRDataset(two augmented views) -> DataLoader(batch_size, shuffle) -> per batch
     ``z_i = model(x_i); z_j = model(x_j); loss = nt_xent_loss(z_i, z_j); backward; Adam(lr).step()``.
@@ -105,6 +106,8 @@ def pretrain_simclr(patch_dir: str, epochs: int = 200, batch_size: int = 512, lr
     ``device_aug`` (additive): the decoded patches stay in HBM and the two views of every step are made by
     ``hipac_augment_views`` (augment.py: Pillow's arithmetic, host-drawn parameters) instead of DataLoader workers -- the
     host pipeline delivers ~1 k view pairs/s, the native step consumes 3 k (fp32) to 14 k (fp16).
+    ``hed_sigma`` > 0 (additive, ``--aug_hed``; needs ``device_aug`` or ``pool``): both views of every pair also get a HED stain
+    map of their own (``augment_hed``), drawn from a generator keyed by ``hed_seed``.
     Returns (SimCLRModel with the trained weights, list of per-epoch mean losses)."""
     from torch.utils.data import DataLoader
 
@@ -114,10 +117,12 @@ def pretrain_simclr(patch_dir: str, epochs: int = 200, batch_size: int = 512, lr
     from .train_native import NativeSimCLRTrainer
 
     rank, world = rank_world()
+    if hed_sigma and pool is None and not device_aug:
+        raise ValueError("hed_sigma needs the device input pipeline (device_aug or pool): the host transforms have no HED stage")
     if pool is not None:  # (additive) an ``augment.DevicePatchPool`` made elsewhere, e.g. straight from the slides: no PNG tree
         from .augment import DeviceSimCLRLoader
 
-        loader = DeviceSimCLRLoader(pool, batch_size, shuffle=True, seed=0, rank=rank, world=world)
+        loader = DeviceSimCLRLoader(pool, batch_size, shuffle=True, seed=0, rank=rank, world=world, hed_sigma=hed_sigma, hed_seed=hed_seed)
         base = ds = None
     else:
         base = PatchDataset(patch_dir, transform=None)
@@ -128,7 +133,7 @@ def pretrain_simclr(patch_dir: str, epochs: int = 200, batch_size: int = 512, lr
         from .augment import DevicePatchPool, DeviceSimCLRLoader
 
         loader = DeviceSimCLRLoader(DevicePatchPool.from_patch_dataset(base, device=device, workers=max(1, num_workers)), batch_size,
-                                    shuffle=True, seed=0, rank=rank, world=world)
+                                    shuffle=True, seed=0, rank=rank, world=world, hed_sigma=hed_sigma, hed_seed=hed_seed)
     elif world > 1:
         loader = DataLoader(ds, batch_sampler=RankBatchSampler(len(ds), batch_size, rank, world, True, 0), num_workers=num_workers)
     else:

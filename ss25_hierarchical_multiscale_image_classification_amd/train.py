@@ -71,11 +71,12 @@ class _PoolView:
 
 
 def get_device_loaders(slides, level: int = 3, test_ratio: float = 0.2, batch_size: int = 512, balanced: bool = False,
-                       rank: int = 0, world: int = 1, stride: Optional[int] = None):
+                       rank: int = 0, world: int = 1, stride: Optional[int] = None, hed_sigma: float = 0.0, hed_seed: int = 0):
     """``get_dataloaders`` without the PNG tree: the kept windows of ``level`` go from the slides in HBM straight into one
     ``DevicePatchPool`` (``--patch``'s PNGs are lossless: the same pixels and labels), the split is the same slide-level
     split (sorted slide names, random_state=42), ``balanced`` draws the same number of patches per class
-    (src/main.py:432-438), the validation set is balanced with default_rng(42) (:446-450)."""
+    (src/main.py:432-438), the validation set is balanced with default_rng(42) (:446-450).  ``hed_sigma`` / ``hed_seed``
+    (additive, ``--aug_hed``): HED stain maps for the training loader's patches; the validation loader never gets them."""
     from sklearn.model_selection import train_test_split
 
     from .augment import DeviceClassifierLoader, DevicePatchPool
@@ -106,7 +107,8 @@ def get_device_loaders(slides, level: int = 3, test_ratio: float = 0.2, batch_si
         rng = np.random.default_rng(42)
         val_idx = val_idx[np.concatenate([rng.choice(tum, n_min, replace=False), rng.choice(nor, n_min, replace=False)])]
     train_ds, val_ds = _PoolView(pool, train_idx), _PoolView(pool, val_idx.tolist())
-    return (DeviceClassifierLoader(pool, batch_size, shuffle=True, augment=True, seed=0, rank=rank, world=world, indices=train_idx),
+    return (DeviceClassifierLoader(pool, batch_size, shuffle=True, augment=True, seed=0, rank=rank, world=world, indices=train_idx,
+                                   hed_sigma=hed_sigma, hed_seed=hed_seed),
             DeviceClassifierLoader(pool, batch_size, shuffle=False, augment=False, rank=rank, world=world, indices=val_idx.tolist()),
             train_ds, val_ds, pool)
 
@@ -139,7 +141,7 @@ def train_resnet_classifier(patch_dir: str, strategy: Optional[str] = None, epoc
                             save_path: Optional[str] = None, device: str = "cuda", simclr_epochs: int = 200,
                             simclr_path: str = "simclr_encoder.pth", max_steps: Optional[int] = None,
                             train_precision: str = "fp16", simclr_precision: str = "fp32", device_aug: bool = False,
-                            slides=None, level: int = 3):
+                            slides=None, level: int = 3, hed_sigma: float = 0.0, hed_seed: int = 0):
     """``train_resnet_classifier`` (strategy None, 30 epochs, src/main.py:472-534) and
     ``train_resnet_classifier_strategic`` (5 epochs, :536-606).  The training step runs on the native kernels
     (``train_native.NativeClassifierTrainer``) in ``train_precision``: "fp16" (default) = the reference's
@@ -150,21 +152,35 @@ def train_resnet_classifier(patch_dir: str, strategy: Optional[str] = None, epoc
     decoded patches stay in HBM and every batch is transformed on the device (``augment.DeviceClassifierLoader``; SimCLR
     pre-training: ``augment.DeviceSimCLRLoader``) instead of in DataLoader workers.  ``slides`` (additive; a list of
     ``extract.DeviceSlide``): no PNG tree at all -- the kept windows of ``level`` go from the pyramids in HBM into the pool
-    (``get_device_loaders``), ``patch_dir`` is not read."""
+    (``get_device_loaders``), ``patch_dir`` is not read.  ``hed_sigma`` > 0 (additive, ``--aug_hed``; needs the device input
+    pipeline): HED stain augmentation of every training patch and of both SimCLR views (``augment_hed``), its draws keyed by
+    ``hed_seed``; validation is not augmented."""
+    from .augment_hed import check_sigma
     from .dist import all_reduce_sum_scalars, rank_world
     from .train_native import NativeClassifierTrainer
     from .weights import canonical_state_dict
 
     rank, world = rank_world()  # > 1 under ``main.py --world_size N``: one process per GPU, global batch = batch_size
     epochs = epochs if epochs is not None else (30 if strategy is None else 5)  # :494 / :575
+    hed_sigma = check_sigma(hed_sigma)
+    if hed_sigma > 0.0 and slides is None and not device_aug:
+        raise ValueError("hed_sigma needs the device input pipeline (device_aug or slides): the host transforms have no HED stage")
     pool_all = None
     if slides is not None:
         train_loader, val_loader, train_ds, val_ds, pool_all = get_device_loaders(slides, level, 0.2, batch_size,
-                                                                                   balanced=strategy == "balanced", rank=rank, world=world)
+                                                                                   balanced=strategy == "balanced", rank=rank, world=world,
+                                                                                   hed_sigma=hed_sigma, hed_seed=hed_seed)
         device_aug = False  # the loaders are device loaders already
     else:
         train_loader, val_loader, train_ds, val_ds = get_dataloaders(patch_dir, 0.2, batch_size,
                                                                      balanced=strategy == "balanced", rank=rank, world=world)
+        if hed_sigma > 0.0 and train_ds.image_paths:  # refused before any pre-training is spent: at other sizes the classifier loop keeps the host transforms
+            from PIL import Image
+
+            with Image.open(train_ds.image_paths[0]) as im:
+                if im.size != (224, 224):
+                    raise ValueError(f"hed_sigma: the patches of {patch_dir} are {im.size[0]} x {im.size[1]}; the device pipeline of "
+                                     "the classifier loops takes 224-pixel patches, and the host transforms have no HED stage")
     dev = torch.device(device)
     model = ResNet18Classifier().set_precision(precision)
     if strategy == "self_supervised":
@@ -174,7 +190,7 @@ def train_resnet_classifier(patch_dir: str, strategy: Optional[str] = None, epoc
             # the final checkpoint goes to simclr_path itself, whatever its basename
             pretrain_simclr(patch_dir, epochs=simclr_epochs, batch_size=batch_size, device=device,
                             out_dir=os.path.dirname(simclr_path) or ".", max_steps=max_steps, final_path=simclr_path,
-                            precision=simclr_precision, device_aug=device_aug, pool=pool_all)
+                            precision=simclr_precision, device_aug=device_aug, pool=pool_all, hed_sigma=hed_sigma, hed_seed=hed_seed)
             if world > 1:
                 torch.distributed.barrier()  # rank 0 wrote the file
         if not os.path.exists(simclr_path):
@@ -192,10 +208,13 @@ def train_resnet_classifier(patch_dir: str, strategy: Optional[str] = None, epoc
 
         tr_pool = DevicePatchPool.from_patch_dataset(train_ds, device=device)
         if tr_pool.P == OUT:
-            train_loader = DeviceClassifierLoader(tr_pool, batch_size, shuffle=True, augment=True, seed=0, rank=rank, world=world)
+            train_loader = DeviceClassifierLoader(tr_pool, batch_size, shuffle=True, augment=True, seed=0, rank=rank, world=world,
+                                                  hed_sigma=hed_sigma, hed_seed=hed_seed)
             val_loader = DeviceClassifierLoader(DevicePatchPool.from_patch_dataset(val_ds, device=device), batch_size, shuffle=False,
                                                 augment=False, rank=rank, world=world)
         else:  # the rotation / jitter of train_transform act at the source resolution before the resize: host transforms there
+            if hed_sigma > 0.0:
+                raise ValueError(f"hed_sigma: {tr_pool.P}-pixel patches keep the host transforms, which have no HED stage")
             if rank == 0:
                 print(f"[INFO] --device_aug: {tr_pool.P}-pixel patches keep the host transforms (the device pipeline of the "
                       f"classifier loops takes 224-pixel patches)")
