@@ -2,7 +2,8 @@
 // restates them in numpy): one workgroup per replicate, integers only.
 //
 // A replicate
-//   1. draws its S case indices with Philox into the count table cnt[S] in LDS (integer atomics: order-independent);
+//   1. draws its S case indices with Philox into the count table cnt[S] in LDS (integer atomics: order-independent;
+//      ci_draws.h, shared with evaluate.hip);
 //   2. reduces over the cases: the tumour total, the drawn positives / negatives, the smallest present threshold index
 //      minP (from the per-case minima the host supplies), and twice the Mann-Whitney U from an exclusive prefix of the
 //      negatives' weights over the slides in score order (negpre[], LDS) and the host's tie groups;
@@ -22,15 +23,13 @@
 #include <limits.h>
 
 #include "../../include/hipac_eval_ci.h"
-#include "philox.h"
+#include "ci_draws.h"
 
 namespace hipac {
 
-constexpr int kCiThreads = 256;
 constexpr int kCiPerThread = 4;
 constexpr int kCiChunk = kCiThreads * kCiPerThread;  // events per step of every walk over the table
 constexpr int kCiWaves = kCiThreads / 64;
-constexpr int kCiSite = 2;  // Philox counter word 3: sites 0 and 1 are the dropout masks
 constexpr int kCiScratch = 64;  // words of reduction scratch and per-rate results behind the two tables
 static_assert(kCiChunk == HIPAC_EVAL_CI_CHUNK, "the header states the chunk");
 
@@ -88,19 +87,6 @@ __device__ __forceinline__ int ci_block_min(int v, int* scratch) {
   for (int i = 0; i < kCiWaves; ++i) t = min(t, scratch[i]);
   __syncthreads();
   return t;
-}
-
-// cnt[s] = how often the S draws of replicate r pick case s; ends with a barrier
-__device__ __forceinline__ void ci_draw_counts(int* cnt, int S, uint32_t r, uint32_t k0, uint32_t k1) {
-  for (int s = threadIdx.x; s < S; s += kCiThreads) cnt[s] = 0;
-  __syncthreads();
-  for (int q = threadIdx.x; q * 4 < S; q += kCiThreads) {
-    const Philox4 w = philox4x32_10((uint32_t)q, r, 0u, (uint32_t)kCiSite, k0, k1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (q * 4 + i < S) atomicAdd(&cnt[__umulhi(w.w[i], (uint32_t)S)], 1);  // (word * S) >> 32 < S
-  }
-  __syncthreads();
 }
 
 // four consecutive entries a[k .. k + 3] of an event array, `fill` past its end

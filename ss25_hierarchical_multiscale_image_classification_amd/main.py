@@ -73,6 +73,15 @@ then not read.  ``--predict_mil`` reads the levels from the saved model; ``--mil
 class-weighted logistic-regression probe (Newton's method) on ``patch_features_<L>.npy`` / ``patch_labels_<L>.npy`` of
 ``--patch_level`` -> ``results/validate_<L>.json``; ``--validate_save_pca`` adds ``results/pca_<L>.npy``.  No t-SNE.
 
+``--eval_patches`` is the reference's ``--evaluate`` stage (src/main.py:974-1015) under a new name (``--evaluate`` itself
+stays out of scope): the checkpoint of ``--weights`` (default ``src/models/resnet18_patch_classifier.pth``, where ``--train``
+saves) is scored on the validation set of ``--train`` -- the PNG tree of ``--patch_level``, its device pool under
+``--device_aug``, or the slides under ``--from_slides`` -- and ``evaluate.py`` writes ``results/evaluate_<L>.json``: confusion
+matrix, the quantities of the reference's ``src/utils/metrics.py``, a ROC / AUC and average precision over 4096 probability
+bins, and a per-slide table, all tallied on the device in integers.  ``--eval_threshold T`` decides by ``p > T`` instead of the
+argmax, ``--eval_unbalanced`` scores every patch of the validation slides, ``--eval_bootstrap B`` / ``--eval_ci`` / ``--seed``
+add percentile intervals from B resamples of the validation slides.
+
 Everything else outside the hot path (download, plots) is out of scope and the
 corresponding reference flags are accepted but answered with a clear message.
 """
@@ -103,6 +112,23 @@ def _eval_ci(text: str) -> float:
     if not 0.0 < v < 100.0:
         raise argparse.ArgumentTypeError(f"takes a percentage above 0 and below 100, got {text}")
     return v
+
+
+def _eval_threshold(text: str) -> float:
+    v = float(text)
+    if not 0.0 < v < 1.0:
+        raise argparse.ArgumentTypeError(f"takes a probability strictly between 0 and 1, got {text}")
+    return v
+
+
+def check_eval_patches_args(parser, args):
+    """--eval_threshold / --eval_unbalanced without --eval_patches are argparse errors (exit status 2): a flag that is dropped
+    silently would be worse than none."""
+    if not args.eval_patches:
+        if args.eval_threshold is not None:
+            parser.error(f"--eval_threshold {args.eval_threshold:g} is an option of --eval_patches")
+        if args.eval_unbalanced:
+            parser.error("--eval_unbalanced is an option of --eval_patches")
 
 
 def _aug_hed(text: str) -> float:
@@ -145,6 +171,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--run_evaluation: percentile-bootstrap intervals of the score, the six sensitivities (and the AUC) over B "
                         "resamples of the cases, drawn on the device and keyed by --seed -> bootstrap_results.json (0 = off, at most 65536)")
     p.add_argument("--eval_ci", type=_eval_ci, default=95.0, metavar="PCT", help="--eval_bootstrap: the interval in percent (above 0, below 100)")
+    p.add_argument("--eval_patches", action="store_true",
+                   help="the reference's --evaluate stage (src/main.py:974-1015): score the checkpoint of --weights (default "
+                        "src/models/resnet18_patch_classifier.pth) on the validation patches of --train, tallied on the device -> "
+                        "results/evaluate_<L>.json; --eval_bootstrap / --eval_ci / --seed add intervals over resamples of the slides")
+    p.add_argument("--eval_threshold", type=_eval_threshold, default=None, metavar="T",
+                   help="--eval_patches: a patch is called tumour when its probability is > T (strictly between 0 and 1; default: "
+                        "the network's argmax)")
+    p.add_argument("--eval_unbalanced", action="store_true",
+                   help="--eval_patches: score every patch of the validation slides instead of the class-balanced set of --train")
     p.add_argument("--validate", action="store_true",
                    help="sanity check of the feature files of --patch_level in the working directory (src/main.py:1017-1070): "
                         "PCA and a logistic-regression probe on the device -> results/validate_<L>.json (rank 0)")
@@ -771,6 +806,71 @@ def cmd_validate(args) -> int:
     return rc
 
 
+def eval_patches_sources(args):
+    """(weights path, level, patch_dir) of --eval_patches."""
+    level = int(args.patch_level) if args.patch_level != "all" else 3  # as for --train
+    weights = args.weights or os.path.join(os.getcwd(), "src", "models", "resnet18_patch_classifier.pth")  # src/main.py:978
+    return weights, level, os.path.join(data_root(args), "patches", f"level_{level}")
+
+
+def check_eval_patches_inputs(args, trained: bool = False, patched: bool = False) -> int:
+    """0, or 1 after the reference's message for a missing checkpoint / a missing patch tree; no GPU is touched.  ``trained`` /
+    ``patched``: the same invocation makes the file / the tree first, so its absence now means nothing."""
+    weights, _, patch_dir = eval_patches_sources(args)
+    if not trained and not os.path.exists(weights):
+        print(f"[ERROR] Model file '{weights}' does not exist. Please train the model first.")
+        return 1
+    if args.from_slides:
+        missing = not list_slides(args)
+    else:
+        missing = not patched and not (os.path.isdir(patch_dir) and any(f.endswith(".png") for _, _, fs in os.walk(patch_dir) for f in fs))
+    if missing:
+        print("[ERROR] Patches must be extracted before evaluation.")
+        return 1
+    return 0
+
+
+def cmd_eval_patches(args) -> int:
+    """--eval_patches: the reference's evaluate_resnet_classifier (src/main.py:974-1015); evaluate.py has the driver."""
+    import json
+
+    from . import evaluate
+    from .dist import rank_world
+
+    rc = check_eval_patches_inputs(args)
+    if rc:
+        return rc
+    weights, level, patch_dir = eval_patches_sources(args)
+    rank, world = rank_world()
+    if world == 1 and args.seed is None:
+        _seed_everything(0)  # the dataset's shuffle decides which patches the balancing keeps: two runs score the same set
+    if rank == 0:
+        print("[INFO] Evaluating ResNet18 classifier...", flush=True)
+    slides = None
+    if args.from_slides:  # every rank holds every slide: batches are shared out, not slides
+        slides = [s for s in (try_open(name, make) for name, make in list_slides(args)) if s is not None]
+    try:
+        doc = evaluate.evaluate_patches(patch_dir, slides=slides, level=level, weights=weights, precision=args.precision,
+                                        batch_size=args.batch_size, threshold=args.eval_threshold, unbalanced=args.eval_unbalanced,
+                                        bootstrap=args.eval_bootstrap, ci=args.eval_ci, seed=0 if args.seed is None else args.seed,
+                                        device_aug=args.device_aug)
+    except evaluate.EvaluateError as e:
+        print(f"[ERROR] --eval_patches: {e}")
+        return e.status
+    if doc is None:  # not rank 0
+        return 0
+    (tn, fp), (fn, tp) = doc["confusion_matrix"]
+    print(f"[INFO] Classifier accuracy on validation patches: {doc['accuracy']:.4f}")
+    print(f"[INFO] Confusion matrix over {doc['n']} patches of {len(doc['per_slide'])} slides: TN {tn}, FP {fp}, FN {fn}, TP {tp}")
+    for line in evaluate.bootstrap_lines(doc) if "bootstrap" in doc else ():
+        print(line)
+    os.makedirs("results", exist_ok=True)
+    with open(os.path.join("results", f"evaluate_{level}.json"), "w") as f:
+        json.dump(doc, f, indent=1)
+    print(f"[INFO] Results written to results/evaluate_{level}.json")
+    return 0
+
+
 def _seed_everything(seed: int):
     import random
 
@@ -785,6 +885,7 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     check_mil_args(parser, args)
     check_aug_args(parser, args)
+    check_eval_patches_args(parser, args)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")
@@ -804,6 +905,8 @@ def main(argv=None) -> int:
     except ValueError as e:
         print(f"[ERROR] --stain_norm: {e}")
         return 2
+    if args.eval_patches and check_eval_patches_inputs(args, trained=args.train or args.train_strategy, patched=args.patch):
+        return 1  # refused before any process is started or any GPU touched
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.world_size > 1 and not under_launcher:
         # parent: start one fresh process per GPU and supervise them; nothing here may initialise the GPU
@@ -851,6 +954,9 @@ def _dispatch(args) -> int:
         rc = cmd_train(args, None) or rc
     if args.train_strategy:
         rc = cmd_train(args, args.strategy) or rc
+    if args.eval_patches:
+        _rendezvous()  # rank 0 of --train wrote the checkpoint
+        rc = cmd_eval_patches(args) or rc
     if args.detect:
         rc = cmd_detect(args) or rc
         _rendezvous()  # --run_evaluation on rank 0 reads every rank's CSVs

@@ -21,12 +21,13 @@ SAMPLES_PER_CLASS = 7480  # src/main.py:50
 
 
 def get_dataloaders(patch_dir: str, test_ratio: float = 0.2, batch_size: int = 512, balanced: bool = False,
-                    rank: int = 0, world: int = 1, seed: int = 0):
+                    rank: int = 0, world: int = 1, seed: int = 0, balance_val: bool = True):
     """src/main.py:412-470: slide-level split (random_state=42), tumour patches
     augmented, normal patches not, validation set balanced with default_rng(42).
     ``world > 1`` (one process per GPU): every rank builds the same datasets (the caller seeds ``random`` identically on
     all ranks) and draws its share of every global batch (``dist.RankBatchSampler``: the chunk DataParallel's scatter
-    gives replica ``rank``); the validation batches are shared out the same way, unshuffled."""
+    gives replica ``rank``); the validation batches are shared out the same way, unshuffled.  ``balance_val=False`` (additive,
+    ``--eval_patches --eval_unbalanced``): the validation set keeps every patch of its slides."""
     from sklearn.model_selection import train_test_split
 
     from .dist import RankBatchSampler
@@ -43,7 +44,7 @@ def get_dataloaders(patch_dir: str, test_ratio: float = 0.2, batch_size: int = 5
                           normal_transform=eval_transform())
     labels = np.array(val_ds.labels)
     tum, nor = np.where(labels == 1)[0], np.where(labels == 0)[0]
-    if len(tum) and len(nor):
+    if balance_val and len(tum) and len(nor):
         n_min = min(len(tum), len(nor))
         rng = np.random.default_rng(42)
         sel = np.concatenate([rng.choice(tum, n_min, replace=False), rng.choice(nor, n_min, replace=False)])
@@ -71,12 +72,14 @@ class _PoolView:
 
 
 def get_device_loaders(slides, level: int = 3, test_ratio: float = 0.2, batch_size: int = 512, balanced: bool = False,
-                       rank: int = 0, world: int = 1, stride: Optional[int] = None, hed_sigma: float = 0.0, hed_seed: int = 0):
+                       rank: int = 0, world: int = 1, stride: Optional[int] = None, hed_sigma: float = 0.0, hed_seed: int = 0,
+                       balance_val: bool = True):
     """``get_dataloaders`` without the PNG tree: the kept windows of ``level`` go from the slides in HBM straight into one
     ``DevicePatchPool`` (``--patch``'s PNGs are lossless: the same pixels and labels), the split is the same slide-level
     split (sorted slide names, random_state=42), ``balanced`` draws the same number of patches per class
     (src/main.py:432-438), the validation set is balanced with default_rng(42) (:446-450).  ``hed_sigma`` / ``hed_seed``
-    (additive, ``--aug_hed``): HED stain maps for the training loader's patches; the validation loader never gets them."""
+    (additive, ``--aug_hed``): HED stain maps for the training loader's patches; the validation loader never gets them.
+    ``balance_val=False`` (additive, ``--eval_patches --eval_unbalanced``): the validation set keeps every patch of its slides."""
     from sklearn.model_selection import train_test_split
 
     from .augment import DeviceClassifierLoader, DevicePatchPool
@@ -102,7 +105,7 @@ def get_device_loaders(slides, level: int = 3, test_ratio: float = 0.2, batch_si
     val_idx = np.array([i for i, n in enumerate(pool.slide_names) if n in va_set], np.int64)
     labels = np.array([pool.labels[i] for i in val_idx])
     tum, nor = np.where(labels == 1)[0], np.where(labels == 0)[0]
-    if len(tum) and len(nor):
+    if balance_val and len(tum) and len(nor):
         n_min = min(len(tum), len(nor))
         rng = np.random.default_rng(42)
         val_idx = val_idx[np.concatenate([rng.choice(tum, n_min, replace=False), rng.choice(nor, n_min, replace=False)])]
