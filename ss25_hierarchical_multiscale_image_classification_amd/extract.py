@@ -457,11 +457,17 @@ def score_slide(slide: DeviceSlide, net: capi.PackedResNet18, levels: Sequence[i
     return feats, logits, preds, metas
 
 
-def save_patch_pngs(slide: DeviceSlide, level: int, out_dir: str, stride: Optional[int] = None, tissue=None) -> int:
+def save_patch_pngs(slide: DeviceSlide, level: int, out_dir: str, stride: Optional[int] = None, tissue=None, encoder: str = "host") -> int:
     """Optional reference-compatible output: write every kept window as
     ``<out_dir>/<slide>/<slide>_x{x}_y{y}_{label}.png`` (src/main.py:722-726).  This is
     the slow, host-bound leg (D2H copy + PNG encode) kept for downstream tools; the fused
-    path never touches disk (PNG is lossless, so skipping it changes nothing)."""
+    path never touches disk (PNG is lossless, so skipping it changes nothing).
+    ``encoder="device"``: the same scan, names and skipping of files that exist, but the windows are encoded on the device in
+    batches (``png_encode.iter_encoded``) and the host only writes the compressed bytes."""
+    if encoder == "device":
+        return _save_patch_pngs_device(slide, level, out_dir, stride, tissue)
+    if encoder != "host":
+        raise capi.HipacError(f"save_patch_pngs: encoder {encoder!r} (host or device)")
     from PIL import Image
 
     scan = scan_level(slide, level, stride=stride, tissue=tissue)
@@ -484,4 +490,34 @@ def save_patch_pngs(slide: DeviceSlide, level: int, out_dir: str, stride: Option
             canvas[:ph, :pw] = img[y : y + ph, x : x + pw].cpu().numpy()
             Image.fromarray(canvas, "RGB").save(path)
         n += 1
+    return n
+
+
+
+def _save_patch_pngs_device(slide: DeviceSlide, level: int, out_dir: str, stride, tissue) -> int:
+    """The device leg of ``save_patch_pngs``: files that exist are left alone and their windows are not encoded."""
+    from . import png_encode
+
+    scan = scan_level(slide, level, stride=stride, tissue=tissue)
+    P = scan.patch_size
+    width, height = slide.level_dimensions[level]
+    save_dir = os.path.join(out_dir, slide.name)
+    os.makedirs(save_dir, exist_ok=True)
+    xy = scan.xy.cpu().numpy()
+    keep = scan.keep.cpu().numpy().astype(bool)
+    lab = scan.labels.cpu().numpy()
+    n, todo_xy, todo_path = 0, [], []
+    for (x, y), k, l in zip(xy, keep, lab):
+        if not k:
+            continue
+        path = os.path.join(save_dir, f"{slide.name}_x{x}_y{y}_{LABEL_NAMES[int(l)]}.png")
+        if not os.path.exists(path):
+            todo_xy.append((int(x), int(y)))
+            todo_path.append(path)
+        n += 1
+    if todo_xy:
+        for lo, files in png_encode.iter_encoded(slide.levels[level], width, height, np.array(todo_xy, np.int32), P):
+            for path, data in zip(todo_path[lo:lo + len(files)], files):
+                with open(path, "wb") as f:
+                    f.write(data)
     return n

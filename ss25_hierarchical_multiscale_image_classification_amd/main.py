@@ -46,6 +46,14 @@ gets a random HED stain map of its own in optical-density space, alpha ~ U(1 - S
 stain, inside the colour kernel.  Keyed by ``--seed``; validation is never augmented; refused without the device pipeline.
 Default 0: no byte of any output and no call path changes.
 
+``--png_encoder device`` moves the PNG encoding of ``--patch --write_png`` to the device (``png_encode.py``,
+``include/hipac_png.h``): the row filter (the cheapest of the five types per row), deflate (distance-1 run matches and one stored,
+fixed or dynamic Huffman block per band of at most 24 KiB of filtered rows, whichever is smallest) and both checksums run in HBM
+for batches of windows, one copy per batch brings the compressed bytes back and the host only writes the files.  The same file
+names, the same pixels after decoding, the same skipping of files that exist; the bytes of the files differ from Pillow's (run
+matches only, one IDAT chunk per band, the project's own Huffman builder).  Refused without ``--write_png``.  Default ``host``: no
+byte written or printed changes.
+
 ``--run_evaluation`` scores ``./models/first_model/model_predictions_csv/*.csv`` (written by ``--detect``, or by
 ``features.save_froc_csv`` with one line per window) against ``<data_root>/test/mask`` with the CAMELYON16 FROC script's rules, the
 evaluation masks made on the device (``froc.py``); it writes ``froc_results.json`` (and ``froc.png``).
@@ -150,6 +158,13 @@ def check_aug_args(parser, args):
             parser.error(f"--aug_hed {args.aug_hed:g} needs the device input pipeline: give --device_aug or --from_slides")
 
 
+def check_png_args(parser, args):
+    """--png_encoder device without --write_png is refused as an argparse error (exit status 2): there would be nothing to
+    encode, and a flag that is dropped silently would be worse than none."""
+    if args.png_encoder != "host" and not args.write_png:
+        parser.error(f"--png_encoder {args.png_encoder} is an option of --patch --write_png")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="HiPAC hot path on MI355X (patch extraction + ResNet18 scoring)")
     # --- the reference's surface (src/main.py:1075-1093) ---
@@ -192,6 +207,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_root", type=str, default=None)
     p.add_argument("--synthetic", action="append", default=[], metavar="W,H,SEED[,NAME]")
     p.add_argument("--write_png", action="store_true")
+    p.add_argument("--png_encoder", choices=["host", "device"], default="host",
+                   help="--patch --write_png: who encodes the patch PNGs; host = Pillow on the host, one window at a time; device = "
+                        "filter, deflate and checksums on the device (png_encode.py), only compressed bytes are copied back")
     p.add_argument("--precision", choices=["bf16", "fp16", "fp16x3", "fp16q8", "fp32"], default="bf16",
                    help="MFMA operand type; fp16x3 = parity mode (fp16 pairs, three products per term: the reference's fp32 "
                         "results to 1e-3 at ~1/3 of the bf16 throughput); fp16q8 = the faster parity mode (the same pairs, cross "
@@ -445,7 +463,10 @@ def cmd_patch(args):
                      sums=scan.sums.cpu().numpy().astype(np.uint32), patch_size=scan.patch_size, level=level)
             n = int(scan.keep.sum().item())
             if args.write_png:
-                save_patch_pngs(slide, level, level_dir, stride=args.stride, tissue=tissue)
+                if args.png_encoder == "host":
+                    save_patch_pngs(slide, level, level_dir, stride=args.stride, tissue=tissue)
+                else:
+                    save_patch_pngs(slide, level, level_dir, stride=args.stride, tissue=tissue, encoder=args.png_encoder)
             print(f"[INFO] Patch extraction complete for {slide.name} at level {level}. Total patches: {n}")
         report_tissue(args, tissue, slide)
         report_stain(args, stain, tissue, slide)
@@ -886,6 +907,7 @@ def main(argv=None) -> int:
     check_mil_args(parser, args)
     check_aug_args(parser, args)
     check_eval_patches_args(parser, args)
+    check_png_args(parser, args)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")
