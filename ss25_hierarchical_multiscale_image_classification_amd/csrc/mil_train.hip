@@ -14,6 +14,8 @@
 //                              over H),  dV = dH^T X (f32 MFMA, reduction over rows), db_V = sum dH_i, dU = sum ds_i H_i,
 //                              db_U = sum ds_i.  Two sweeps over X: the row dot products, then dV (DESIGN.md 3.3b has the
 //                              measurement against the form that keeps P = X W1^T from the forward and sweeps once).
+//                              pooled_b . g_b is taken as sum_j a_j (x_j . g_b) / sum_j a_j from the kept row dot products
+//                              (mt_rowdot_kernel, mt_bag_cdot_kernel), so that sum_i ds_i of a bag rounds to 0.
 // mean / max pooling have no parameter in front of the classifier: the features are data, not parameters, so their
 // backward ends at dL/dpooled.
 // The classifier, the cross-entropy and Adam are hipac.h's hipac_linear_* / hipac_cross_entropy_fwd_bwd / hipac_adam_step.
@@ -62,7 +64,7 @@ static MilHeadPlan make_mil_train_plan(const hipac_mil_params_t* p, int pooling,
   q.dlogits = take(B * Cn * 4);
   q.g = take(B * F * 4);
   q.ce = take((2 + 8 * ((B + 255) / 256)) * 4);
-  q.cdot = take(B * 4);
+  q.cdot = take(B * 8);  // doubles here (mt_bag_cdot_kernel)
   q.part = take((size_t)q.nseg * F * 4);
   if (att) {
     q.scores = take((size_t)n * 4);
@@ -247,43 +249,90 @@ __global__ __launch_bounds__(256) void mt_pool_combine_kernel(const float* __res
   }
 }
 
-// cdot[b] = pooled_b . g_b = sum_j a_j (x_j . g_b): the softmax backward's second term, known before any row is read
+// cdot[b] = pooled_b . g_b = sum_j a_j (x_j . g_b), the softmax backward's second term, as the K-head steps take it
+// (mil_train_launch_cdot): known before any row is read.  The products are added in the order in which their ds kernels add
+// x_i . g_b: lane c takes the float4s c, c + 64, ..., then the butterfly.  The two terms of ds_i = a_i (x_i . g_b - cdot_b)
+// then round alike, and in a bag of one row, where a_i is 1 and pooled_b is x_i bit for bit, they are equal bit for bit:
+// ds_i is exactly 0 there, as in exact arithmetic, and not a rounding residue that reaches every attention gradient.
 __global__ __launch_bounds__(256) void mt_cdot_kernel(const float* __restrict__ pooled, const float* __restrict__ g, int F, int B,
                                                       float* __restrict__ cdot) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
+  const f32x4* pb = reinterpret_cast<const f32x4*>(pooled + (size_t)b * F);
+  const f32x4* gb = reinterpret_cast<const f32x4*>(g + (size_t)b * F);
   float v = 0.f;
-  for (int f = lane; f < F; f += 64) v = fmaf(pooled[(size_t)b * F + f], g[(size_t)b * F + f], v);
+  for (int c = lane; c < F / 4; c += 64) {
+    const f32x4 pv = pb[c], gv = gb[c];
+    v = fmaf(pv[0], gv[0], v), v = fmaf(pv[1], gv[1], v), v = fmaf(pv[2], gv[2], v), v = fmaf(pv[3], gv[3], v);
+  }
   v = mil_wave_sum(v);
   if (lane == 0) cdot[b] = v;
 }
 
-// one sweep over the rows of a tile: ds_i = a_i (x_i . g_b - cdot_b); H_i becomes dH_i = ds_i U (1 - H_i^2) in place; the tile's
-// column sums part2[tile] = (sum dH_i [A_pad] | sum ds_i H_i [A_pad] | sum ds_i).  A wave takes rows wave, wave + 4, ...
-__global__ __launch_bounds__(256) void mt_ds_kernel(const float* __restrict__ feats, const int32_t* __restrict__ rows,
-                                                    const int32_t* __restrict__ bag_of, const float* __restrict__ attn,
-                                                    const float* __restrict__ g, const float* __restrict__ cdot,
-                                                    const float* __restrict__ Uw, float* __restrict__ H, int n, int F, int A,
-                                                    int A_pad, float* __restrict__ part2) {
-  __shared__ float red[4][513];
-  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float accV[4] = {0.f, 0.f, 0.f, 0.f}, accU[4] = {0.f, 0.f, 0.f, 0.f}, accB = 0.f;
-  float u[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) u[q] = lane + 64 * q < A ? Uw[lane + 64 * q] : 0.f;
+// The single-head step forms the softmax backward from ONE evaluation of the row dot products, as its closed form has it:
+// ds_i = a_i (t_i - c_b), t_i = x_i . g_b, c_b = sum_j a_j t_j / sum_j a_j (= pooled_b . g_b, sum_j a_j being 1 in exact
+// arithmetic).  sum_i ds_i of a bag is then 0 up to the rounding of its own terms, whatever the rounding of the t_i, and ds_i
+// of a one-row bag is exactly 0.  With c_b taken from pooled_b . g_b, a second evaluation, the sum kept a rounding of the dot
+// products, which is what db_U = sum ds_i and, for small A, db_V = U sum ds_i (1 - H_i^2) consist of.
+
+// t_i = x_i . g_b for the rows of a tile; a wave takes rows wave, wave + 4, ...  The first of the backward's two sweeps over X.
+__global__ __launch_bounds__(256) void mt_rowdot_kernel(const float* __restrict__ feats, const int32_t* __restrict__ rows,
+                                                        const int32_t* __restrict__ bag_of, const float* __restrict__ g, int n, int F,
+                                                        float* __restrict__ rowdot) {
+  const int tile = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int F4 = F / 4;
   for (int rr = wave; rr < kMtTile; rr += 4) {
     const int i = tile * kMtTile + rr;
     if (i >= n) break;
-    const int b = bag_of[i];
     const f32x4* x = reinterpret_cast<const f32x4*>(feats + (size_t)(rows ? rows[i] : i) * F);
-    const f32x4* gb = reinterpret_cast<const f32x4*>(g + (size_t)b * F);
+    const f32x4* gb = reinterpret_cast<const f32x4*>(g + (size_t)bag_of[i] * F);
     float t = 0.f;
     for (int c = lane; c < F4; c += 64) {
       const f32x4 xv = x[c], gv = gb[c];
       t = fmaf(xv[0], gv[0], t), t = fmaf(xv[1], gv[1], t), t = fmaf(xv[2], gv[2], t), t = fmaf(xv[3], gv[3], t);
     }
-    const float ds = attn[i] * (mil_wave_sum(t) - cdot[b]);
+    t = mil_wave_sum(t);
+    if (lane == 0) rowdot[i] = t;
+  }
+}
+
+// c_b = sum_j a_j t_j / sum_j a_j in double, one workgroup per bag: 4 bytes per row twice, like the softmax.  Fixed order:
+// shuffle tree inside a wave, the four waves in order.
+__global__ __launch_bounds__(256) void mt_bag_cdot_kernel(const float* __restrict__ rowdot, const float* __restrict__ attn,
+                                                          const int32_t* __restrict__ offs, double* __restrict__ cdot) {
+  __shared__ double red[2][4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int o0 = offs[b], o1 = offs[b + 1];
+  double num = 0.0, den = 0.0;
+  for (int i = o0 + tid; i < o1; i += 256) {
+    const double a = attn[i];
+    num += a * (double)rowdot[i];
+    den += a;
+  }
+  for (int o = 32; o > 0; o >>= 1) num += __shfl_down(num, o, 64), den += __shfl_down(den, o, 64);
+  if (lane == 0) red[0][wave] = num, red[1][wave] = den;
+  __syncthreads();
+  if (tid == 0)
+    cdot[b] = (((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / (((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]);
+}
+
+// one sweep over the H rows of a tile: ds_i = a_i (t_i - c_b), the difference taken in double; H_i becomes dH_i = ds_i U (1 - H_i^2)
+// in place; the tile's column sums part2[tile] = (sum dH_i [A_pad] | sum ds_i H_i [A_pad] | sum ds_i), added in double and
+// rounded once.  A wave takes rows wave, wave + 4, ...
+__global__ __launch_bounds__(256) void mt_ds_kernel(const float* __restrict__ rowdot, const int32_t* __restrict__ bag_of,
+                                                    const float* __restrict__ attn, const double* __restrict__ cdot,
+                                                    const float* __restrict__ Uw, float* __restrict__ H, int n, int A, int A_pad,
+                                                    float* __restrict__ part2) {
+  __shared__ double red[4][513];
+  const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double accV[4] = {0.0, 0.0, 0.0, 0.0}, accU[4] = {0.0, 0.0, 0.0, 0.0}, accB = 0.0;
+  float u[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) u[q] = lane + 64 * q < A ? Uw[lane + 64 * q] : 0.f;
+  for (int rr = wave; rr < kMtTile; rr += 4) {
+    const int i = tile * kMtTile + rr;
+    if (i >= n) break;
+    const float ds = attn[i] * (float)((double)rowdot[i] - cdot[bag_of[i]]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int j = lane + 64 * q;
@@ -292,11 +341,11 @@ __global__ __launch_bounds__(256) void mt_ds_kernel(const float* __restrict__ fe
         const float hv = j < A ? *hp : 0.f;
         const float dh = ds * u[q] * (1.f - hv * hv);
         *hp = dh;
-        accV[q] += dh;
-        accU[q] = fmaf(ds, hv, accU[q]);
+        accV[q] += (double)dh;
+        accU[q] += (double)ds * (double)hv;
       }
     }
-    accB += ds;
+    accB += (double)ds;
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) red[wave][64 * q + lane] = accV[q], red[wave][256 + 64 * q + lane] = accU[q];
@@ -304,7 +353,7 @@ __global__ __launch_bounds__(256) void mt_ds_kernel(const float* __restrict__ fe
   __syncthreads();
   float* out = part2 + (size_t)tile * (2 * A_pad + 1);
   for (int k = tid; k < 513; k += 256) {
-    const float s = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    const float s = (float)(((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]);
     if (k < 256) {
       if (k < A_pad) out[k] = s;
     } else if (k < 512) {
@@ -587,12 +636,15 @@ int mil_train_run(const hipac_mil_params_t* p, int pooling, const float* feats, 
   rc = mil_classifier_fwd_bwd(p, grads, F, B, labels, class_w, loss, logits, q, ws, att, accumulate, stream, hook, hook_ctx);
   if (rc) return rc;
   if (att) {
-    float* cdot = (float*)(ws + q.cdot);
+    double* cdot = (double*)(ws + q.cdot);
+    float* rowdot = (float*)(ws + q.scores);  // the scores are spent once the softmax has run
     float* part2 = (float*)(ws + q.part2);
     float* slab = (float*)(ws + q.slab);
-    hipLaunchKernelGGL(mt_cdot_kernel, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)pooled, (const float*)g, F, B, cdot);
-    hipLaunchKernelGGL(mt_ds_kernel, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)bag_of, (const float*)a,
-                       (const float*)g, (const float*)cdot, p->attn_U_w, H, n, F, A, q.A_pad, part2);
+    hipLaunchKernelGGL(mt_rowdot_kernel, dim3(q.ntiles), dim3(256), 0, s, feats, rows, (const int32_t*)bag_of, (const float*)g, n, F,
+                       rowdot);
+    hipLaunchKernelGGL(mt_bag_cdot_kernel, dim3(B), dim3(256), 0, s, (const float*)rowdot, (const float*)a, bag_offsets, cdot);
+    hipLaunchKernelGGL(mt_ds_kernel, dim3(q.ntiles), dim3(256), 0, s, (const float*)rowdot, (const int32_t*)bag_of, (const float*)a,
+                       (const double*)cdot, p->attn_U_w, H, n, A, q.A_pad, part2);
     mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 0, A, (float*)grads->attn_V_b, accumulate, s);
     mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, (size_t)q.A_pad, A, (float*)grads->attn_U_w, accumulate, s);
     mil_train_launch_slab_reduce(part2, q.ntiles, q.P2, 2 * (size_t)q.A_pad, 1, (float*)grads->attn_U_b, accumulate, s);
