@@ -24,6 +24,7 @@
 
 #include "../../include/hipac_augment_hed.h"
 #include "augment_hed.h"
+#include "wave_reduce.h"
 
 // Pillow's C is compiled without fused multiply-add: every product below is rounded before it is added
 #pragma clang fp contract(off)
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(kColorThreads) void aug_color_kernel(const unsigned
       if (op == 1) {  // int(mean(L) + 0.5): the sum is exact, the tie-free rounding is integer arithmetic
         int s = 0;
         for (int p = tid; p < NPX; p += kColorThreads) s += luma8(px[3 * p], px[3 * p + 1], px[3 * p + 2]);
-        for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+        s = wave_sum_tree(s);
         if ((tid & 63) == 0) red[tid >> 6] = s;
         __syncthreads();
         long long tot = 0;

@@ -27,6 +27,7 @@
 
 #include "../../include/hipac_deflate.h"
 #include "tile_place.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -367,8 +368,7 @@ __global__ __launch_bounds__(64) void deflate_decode_kernel(const uint8_t* __res
           s1 += b, s2 += (unsigned long long)(n_out - i - k) * b;
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s1 += __shfl_xor(s1, m, 64), s2 += __shfl_xor(s2, m, 64);
+    s1 = wave_sum(s1), s2 = wave_sum(s2);
     const uint32_t a = (uint32_t)((s1 + 1) % 65521u), b = (uint32_t)((s2 + n_out) % 65521u);
     bad = want != (b << 16 | a);
   }

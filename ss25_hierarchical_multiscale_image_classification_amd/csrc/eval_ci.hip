@@ -24,6 +24,7 @@
 
 #include "../../include/hipac_eval_ci.h"
 #include "ci_draws.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -40,54 +41,6 @@ struct CiRates {
 
 static inline int ci_pad4(int S) { return (S + 3) & ~3; }
 static inline size_t ci_lds_bytes(int S) { return (size_t)(2 * ci_pad4(S) + 4 + kCiScratch) * sizeof(int32_t); }
-
-// ---- workgroup helpers: 4 waves of 64, scratch = kCiWaves words (int64: 2 * kCiWaves) of LDS ------------------------
-__device__ __forceinline__ int ci_block_scan_excl(int v, int* scratch, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(inc, d);
-    if (lane >= d) inc += u;
-  }
-  if (lane == 63) scratch[wave] = inc;
-  __syncthreads();
-  int off = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < kCiWaves; ++i) {
-    const int s = scratch[i];
-    off += i < wave ? s : 0;
-    total += s;
-  }
-  __syncthreads();  // scratch is free again
-  return off + inc - v;
-}
-
-__device__ __forceinline__ long long ci_block_sum(long long v, int* scratch) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  long long* s64 = reinterpret_cast<long long*>(scratch);
-  if ((threadIdx.x & 63) == 0) s64[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long t = 0;
-#pragma unroll
-  for (int i = 0; i < kCiWaves; ++i) t += s64[i];
-  __syncthreads();
-  return t;
-}
-
-__device__ __forceinline__ int ci_block_min(int v, int* scratch) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = INT_MAX;
-#pragma unroll
-  for (int i = 0; i < kCiWaves; ++i) t = min(t, scratch[i]);
-  __syncthreads();
-  return t;
-}
 
 // four consecutive entries a[k .. k + 3] of an event array, `fill` past its end
 __device__ __forceinline__ void ci_load4(const int32_t* __restrict__ a, int k, int n, int fill, int (&out)[kCiPerThread]) {
@@ -138,8 +91,8 @@ __global__ __launch_bounds__(kCiThreads) void eval_ci_bootstrap_kernel(
     tum += (long long)c * case_tumours[s];
     if (c > 0) min_p = min(min_p, case_min_own[s]);
   }
-  tum = ci_block_sum(tum, scratch);
-  min_p = ci_block_min(min_p, scratch);
+  tum = block_sum<kCiWaves>(tum, scratch);
+  min_p = block_min<kCiWaves>(min_p, scratch);
 
   // ---- the slides in score order: exclusive prefix of the negatives' weights, then 2 U over the tie groups ----
   const int per = (S + kCiThreads - 1) / kCiThreads;  // <= 16 consecutive positions per thread
@@ -153,7 +106,7 @@ __global__ __launch_bounds__(kCiThreads) void eval_ci_bootstrap_kernel(
     }
   }
   int neg_total;
-  int run = ci_block_scan_excl(neg_local, scratch, neg_total);
+  int run = block_scan_excl<kCiWaves>(neg_local, scratch, neg_total);
   for (int i = 0; i < per; ++i) {
     const int p = t * per + i;
     if (p < S) {
@@ -172,8 +125,8 @@ __global__ __launch_bounds__(kCiThreads) void eval_ci_bootstrap_kernel(
       u2 += (long long)ci_weight(cnt, sc, S) * (2 * below + tied);
     }
   }
-  u2 = ci_block_sum(u2, scratch);
-  const long long pos_total = ci_block_sum(pos_local, scratch);
+  u2 = block_sum<kCiWaves>(u2, scratch);
+  const long long pos_total = block_sum<kCiWaves>((long long)pos_local, scratch);
 
   // ---- pass A: where each rate's FP limit is crossed ----
   long long lim[HIPAC_EVAL_CI_MAX_RATES], lim_max = 0;
@@ -198,7 +151,7 @@ __global__ __launch_bounds__(kCiThreads) void eval_ci_bootstrap_kernel(
       local += w[i];
     }
     int total;
-    const long long before = carry + ci_block_scan_excl(local, scratch, total);
+    const long long before = carry + block_scan_excl<kCiWaves>(local, scratch, total);
     const long long after = before + local;
 #pragma unroll
     for (int R = 0; R < HIPAC_EVAL_CI_MAX_RATES; ++R) {
@@ -272,7 +225,7 @@ __global__ __launch_bounds__(kCiThreads) void eval_ci_bootstrap_kernel(
 #pragma unroll
   for (int R = 0; R < HIPAC_EVAL_CI_MAX_RATES; ++R) {
     if (R < rates.n) {  // uniform: every thread takes part in the reduction
-      const long long v = ci_block_sum(tp[R], scratch);
+      const long long v = block_sum<kCiWaves>(tp[R], scratch);
       if (t == 0) tp_at_rate[(size_t)blockIdx.x * rates.n + R] = v;
     }
   }

@@ -22,6 +22,7 @@
 #include "../../include/hipac_eval_ci.h"
 #include "../../include/hipac_evaluate.h"
 #include "ci_draws.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -34,12 +35,6 @@ constexpr int kEvSeg = kEvBins / (4 * kEvThreads);        // 4 segments of 1024 
 constexpr int kEvScratch = 96;                            // words of LDS behind the counts: 32 scan + 64 reduction
 static_assert(HIPAC_EVALUATE_MAX_GROUPS == HIPAC_EVAL_CI_MAX_CASES, "the slides are drawn as eval_ci's cases are");
 static_assert(kEvSeg * 4 * kEvThreads == kEvBins && kEvSeg * kEvWaves <= 32, "bin ownership of the replicate kernel");
-
-__device__ __forceinline__ unsigned ev_wave_sum(unsigned v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 __global__ __launch_bounds__(kEvThreads) void evaluate_accumulate_kernel(const float* __restrict__ p, const uint8_t* __restrict__ pred,
                                                                           const uint8_t* __restrict__ label,
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(kEvThreads) void evaluate_accumulate_kernel(const f
       atomicAdd(&conf[(size_t)g * 4 + k], 1u);
     }
   }
-  loc0 = ev_wave_sum(loc0), loc1 = ev_wave_sum(loc1), loc2 = ev_wave_sum(loc2), loc3 = ev_wave_sum(loc3), bad = ev_wave_sum(bad);
+  loc0 = wave_sum(loc0), loc1 = wave_sum(loc1), loc2 = wave_sum(loc2), loc3 = wave_sum(loc3), bad = wave_sum(bad);
   if ((threadIdx.x & 63) == 0) {
     if (loc0) atomicAdd(&tally[0], loc0);
     if (loc1) atomicAdd(&tally[1], loc1);
@@ -84,19 +79,6 @@ __global__ __launch_bounds__(kEvThreads) void evaluate_accumulate_kernel(const f
   __syncthreads();
   if (threadIdx.x < 4 && g0 >= 0 && tally[threadIdx.x]) atomicAdd(&conf[(size_t)g0 * 4 + threadIdx.x], tally[threadIdx.x]);
   if (threadIdx.x == 4 && tally[4]) atomicAdd(n_bad, tally[4]);
-}
-
-__device__ __forceinline__ long long ev_block_sum(long long v, int* scratch) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  long long* s64 = reinterpret_cast<long long*>(scratch);
-  if ((threadIdx.x & 63) == 0) s64[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long t = 0;
-#pragma unroll
-  for (int i = 0; i < kEvWaves; ++i) t += s64[i];
-  __syncthreads();
-  return t;
 }
 
 __global__ __launch_bounds__(kEvThreads) void evaluate_bootstrap_kernel(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ conf,
@@ -147,13 +129,7 @@ __global__ __launch_bounds__(kEvThreads) void evaluate_bootstrap_kernel(const ui
 #pragma unroll
   for (int j = 0; j < kEvSeg; ++j) own[j] = inc[j] = h[0][j][0] + h[0][j][1] + h[0][j][2] + h[0][j][3];
 #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-    for (int j = 0; j < kEvSeg; ++j) {
-      const uint32_t u = __shfl_up(inc[j], d);
-      if (lane >= d) inc[j] += u;
-    }
-  }
+  for (int j = 0; j < kEvSeg; ++j) inc[j] = wave_scan_incl(inc[j], lane);
   if (lane == 63) {
 #pragma unroll
     for (int j = 0; j < kEvSeg; ++j) scan[j * kEvWaves + wave] = (int)inc[j];
@@ -180,10 +156,10 @@ __global__ __launch_bounds__(kEvThreads) void evaluate_bootstrap_kernel(const ui
     }
     carry += total;
   }
-  u2 = ev_block_sum(u2, scratch);
-  pos = ev_block_sum(pos, scratch);
+  u2 = block_sum<kEvWaves>(u2, scratch);
+  pos = block_sum<kEvWaves>(pos, scratch);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) cw[k] = ev_block_sum(cw[k], scratch);
+  for (int k = 0; k < 4; ++k) cw[k] = block_sum<kEvWaves>(cw[k], scratch);
   if (t == 0) {
     u2_out[blockIdx.x] = u2;
     n_pos[blockIdx.x] = pos;

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "../../include/hipac_eval.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -160,35 +161,18 @@ __global__ __launch_bounds__(256) void eval_fg_compress_kernel(const uint8_t* __
   L[p] = uf_find(L, p);
 }
 
-// exclusive scan of one int per thread over a 256-thread block; returns the block total in *total
-__device__ __forceinline__ int block_exclusive_scan256(int v, int* total) {
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return base + x - v;
-}
-
 __device__ __forceinline__ bool is_root(const uint8_t* bin, const int* L, int p) { return bin[p] && L[p] == p; }
 
 // roots per chunk of kEvalChunk pixels
 __global__ __launch_bounds__(256) void eval_count_kernel(const uint8_t* __restrict__ bin, int N, const int* __restrict__ L,
                                                          int* __restrict__ cnt) {
+  __shared__ int wsum[4];
   const int p0 = blockIdx.x * kEvalChunk + threadIdx.x * 4;
   int k = 0;
   for (int i = 0; i < 4; ++i)
     if (p0 + i < N && is_root(bin, L, p0 + i)) ++k;
   int total;
-  block_exclusive_scan256(k, &total);
+  block_scan_excl<4>(k, wsum, total);
   if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 
@@ -219,6 +203,7 @@ __global__ __launch_bounds__(1024) void eval_scan_kernel(int* cnt, int n, int32_
 // a root gets -(its number), numbers 1..n in raster order
 __global__ __launch_bounds__(256) void eval_number_kernel(const uint8_t* __restrict__ bin, int N, int* L,
                                                           const int* __restrict__ cnt) {
+  __shared__ int wsum[4];
   const int p0 = blockIdx.x * kEvalChunk + threadIdx.x * 4;
   bool f[4];
   int k = 0;
@@ -227,8 +212,7 @@ __global__ __launch_bounds__(256) void eval_number_kernel(const uint8_t* __restr
     k += f[i];
   }
   int total;
-  const int before = block_exclusive_scan256(k, &total);
-  __syncthreads();  // every root test of the block read L before any root is overwritten
+  const int before = block_scan_excl<4>(k, wsum, total);  // its barriers: every root test of the block read L before any root is overwritten
   int next = cnt[blockIdx.x] + before + 1;
   for (int i = 0; i < 4; ++i)
     if (f[i]) L[p0 + i] = -(next++);

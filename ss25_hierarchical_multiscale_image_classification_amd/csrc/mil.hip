@@ -5,6 +5,7 @@
 // once for its score, once for the pooling -- 4 KB per patch), the arithmetic is ~0.13 MFLOP
 // per patch against 3.6 GFLOP for the ResNet that produced the row.
 #include "common.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -50,8 +51,7 @@ __global__ __launch_bounds__(256) void mil_scores_kernel(const float* __restrict
   const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
 #pragma unroll
   for (int g = 0; g < kMilG; ++g) {
-    float v = acc[g];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const float v = wave_sum_tree(acc[g]);
     if (lane == 0) part[g * nw + wave] = v;
   }
   __syncthreads();
@@ -62,19 +62,7 @@ __global__ __launch_bounds__(256) void mil_scores_kernel(const float* __restrict
   }
 }
 
-__device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float t = __shfl_down(v, o, 64);
-    v = is_max ? fmaxf(v, t) : v + t;
-  }
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < nw; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
+constexpr int kMilBagThreads = 256;  // the launch below; the kernel strides by 256 and reduces over four waves
 
 // one workgroup (256 threads) per bag
 __global__ __launch_bounds__(256) void mil_bag_kernel(const float* __restrict__ feats, const int32_t* __restrict__ offs,
@@ -93,10 +81,10 @@ __global__ __launch_bounds__(256) void mil_bag_kernel(const float* __restrict__ 
   if (pooling == HIPAC_MIL_ATTENTION) {
     float mx = -INFINITY;
     for (int i = o0 + tid; i < o1; i += 256) mx = fmaxf(mx, scores_w[i]);
-    m = block_reduce(mx, true, red);
+    m = block_max_tree<kMilBagThreads / 64>(mx, red);
     float z = 0.f;
     for (int i = o0 + tid; i < o1; i += 256) z += expf(scores_w[i] - m);
-    inv = 1.f / block_reduce(z, false, red);
+    inv = 1.f / block_sum_tree<kMilBagThreads / 64>(z, red);
     // scores[] becomes the softmax weight in place (scratch), so the pooling below reads it back
     for (int i = o0 + tid; i < o1; i += 256) {
       const float w = expf(scores_w[i] - m) * inv;
@@ -174,7 +162,8 @@ extern "C" int hipac_mil_forward(const hipac_mil_params_t* p, int pooling, const
                        p->attn_dim, p->attn_V_w, p->attn_V_b, p->attn_U_w, p->attn_U_b, scores);
     HIPAC_CHECK_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(mil_bag_kernel, dim3(n_bags), dim3(256), 0, s, feats, bag_offsets, p->feature_dim, p->hidden_dim,
+  static_assert(kMilBagThreads == 256, "mil_bag_kernel strides by 256 and reduces over 256 / 64 waves");
+  hipLaunchKernelGGL(mil_bag_kernel, dim3(n_bags), dim3(kMilBagThreads), 0, s, feats, bag_offsets, p->feature_dim, p->hidden_dim,
                      p->num_classes, pooling, scores, p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, logits, attn, pooled);
   HIPAC_CHECK_HIP(hipGetLastError());
   return 0;

@@ -1,31 +1,9 @@
-// Device helpers of the MIL head's kernels (mil_train.hip, mil_heads.hip, mil_gated.hip, mil_levels.hip, mil_dropout.hip).
-// Every reduction here has one fixed order: the results of the kernels depend on the tiling, never on the run.
+// Device helpers of the MIL head's K-head kernels (mil_heads.hip, mil_gated.hip, mil_levels.hip): the load of a lane's score
+// weights and the store of a row sweep's column sums, the four waves added in wave order.
 #pragma once
 #include "common.h"
 
 namespace hipac {
-
-// fixed-order reduction of a 256-thread workgroup (max or sum): shuffle tree inside a wave, the four waves in order through
-// red[4] in LDS; every thread gets the result
-__device__ __forceinline__ float mil_block_reduce(float v, bool is_max, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float t = __shfl_down(v, o, 64);
-    v = is_max ? fmaxf(v, t) : v + t;
-  }
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < 4; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
-
-// butterfly sum over the 64 lanes of a wave; every lane gets the result
-__device__ __forceinline__ float mil_wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // u[k][q] = U[k][lane + 64 q], 0 past A: a lane's four hidden units of the K score vectors
 template <int K>

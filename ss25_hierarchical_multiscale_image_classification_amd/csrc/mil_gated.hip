@@ -17,7 +17,7 @@
 // bag b) = id t + b, partial slabs added in a fixed order; no float atomics.  What does not depend on the gate comes
 // through mil_train_internal.h (row -> bag map, mil_heads.hip's pooling partials, pool combine, M . g, slab sums, and the
 // host side: the workspace plan with two hidden planes, the argument checks, the classifier chain) and mil_device.h (the
-// reductions, the K row dot products and the part2 write-out, shared with mil_heads.hip's kernels); the per-head softmax
+// score weights' load and the part2 write-out, shared with mil_heads.hip's kernels); the per-head softmax
 // has the form of mil_heads.hip's kernel but divides by the sum (see mg_softmax_kernel).  Here: the kernels whose
 // arithmetic has the gate in it, the forward up to the pooled vectors and the two entry points.
 #include "common.h"
@@ -25,6 +25,7 @@
 #include "../../include/hipac_mil_gated.h"
 #include "mil_device.h"
 #include "mil_train_internal.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(256) void mg_score_kernel(const float* __restrict__
       float v = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) v = fmaf(u[k][q], h[q], v);
-      v = mil_wave_sum(v);
+      v = wave_sum(v);
       if (lane == 0) scores[(size_t)i * K + k] = v + Ub[k];
     }
   }
@@ -143,10 +144,10 @@ __global__ __launch_bounds__(256) void mg_softmax_kernel(const float* __restrict
   const int o0 = offs[b], o1 = offs[b + 1];
   float mx = -INFINITY;
   for (int i = o0 + tid; i < o1; i += 256) mx = fmaxf(mx, scores[(size_t)i * K + k]);
-  const float m = mil_block_reduce(mx, true, red);
+  const float m = block_max_tree<4>(mx, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256) z += expf(scores[(size_t)i * K + k] - m);
-  const float zs = mil_block_reduce(z, false, red);
+  const float zs = block_sum_tree<4>(z, red);
   for (int i = o0 + tid; i < o1; i += 256) attn[(size_t)i * K + k] = expf(scores[(size_t)i * K + k] - m) / zs;
 }
 
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(256) void mg_ds_kernel(const float* __restrict__ fe
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      ds[k] = attn[(size_t)i * K + k] * (mil_wave_sum(t[k]) - cdot[b * K + k]);
+      ds[k] = attn[(size_t)i * K + k] * (wave_sum(t[k]) - cdot[b * K + k]);
       accB[k] += ds[k];
     }
 #pragma unroll

@@ -10,7 +10,7 @@
 // X V^T and dV = dH^T X do not depend on K: they are mil_train.hip's kernels, launched through mil_train_internal.h, and
 // so are the row -> bag map, the per-bag combination of the pooling segments (over K F columns instead of F), the
 // M . g products (over B K rows instead of B) and the fixed-order slab sums.  The workspace plan, the argument checks and
-// the classifier chain are mil_train_internal.h's too, the reductions inside the kernels mil_device.h's.  What depends on K
+// the classifier chain are mil_train_internal.h's too, the reductions inside the kernels wave_reduce.h's.  What depends on K
 // is here: the four kernels, the forward up to the pooled vectors and the two entry points.  Every
 // kernel here that touches a feature row reads it ONCE for all K heads: the pooling keeps K f32x4 accumulators per lane
 // (32 VGPRs at K = 8), the backward's row sweep K dot products.  A step therefore sweeps X four times whatever K is
@@ -21,6 +21,7 @@
 #include "../../include/hipac_mil_heads.h"
 #include "mil_device.h"
 #include "mil_train_internal.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) void mh_score_kernel(const float* __restrict__
       float v = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) v = fmaf(u[k][q], h[q], v);
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // not mil_wave_sum: it costs K = 1 a register here
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // not wave_sum: it costs K = 1 a register here (21 -> 22)
       if (lane == 0) scores[(size_t)i * K + k] = v + Ub[k];
     }
   }
@@ -64,10 +65,10 @@ __global__ __launch_bounds__(256) void mh_softmax_kernel(const float* __restrict
   const int o0 = offs[b], o1 = offs[b + 1];
   float mx = -INFINITY;
   for (int i = o0 + tid; i < o1; i += 256) mx = fmaxf(mx, scores[(size_t)i * K + k]);
-  const float m = mil_block_reduce(mx, true, red);
+  const float m = block_max_tree<4>(mx, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256) z += expf(scores[(size_t)i * K + k] - m);
-  const float inv = 1.f / mil_block_reduce(z, false, red);
+  const float inv = 1.f / block_sum_tree<4>(z, red);
   for (int i = o0 + tid; i < o1; i += 256) attn[(size_t)i * K + k] = expf(scores[(size_t)i * K + k] - m) * inv;
 }
 
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void mh_ds_kernel(const float* __restrict__ fe
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      ds[k] = attn[(size_t)i * K + k] * (mil_wave_sum(t[k]) - cdot[b * K + k]);
+      ds[k] = attn[(size_t)i * K + k] * (wave_sum(t[k]) - cdot[b * K + k]);
       accB[k] += ds[k];
     }
 #pragma unroll

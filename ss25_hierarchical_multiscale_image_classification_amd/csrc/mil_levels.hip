@@ -13,7 +13,7 @@
 // combination of the pooling segments (over L F columns), the M . g products (over B L rows) and the fixed-order slab sums are
 // mil_train.hip's, launched through mil_train_internal.h as mil_heads.hip launches them; the workspace plan (with scores and
 // attn one column wide), the argument checks, the classifier chain and the end of the step (db_V | dU | db_U | dV) are that
-// header's as well, the reductions inside the kernels mil_device.h's.  Here: the ml_ kernels, the forward up to the pooled
+// header's as well, the reductions inside the kernels wave_reduce.h's.  Here: the ml_ kernels, the forward up to the pooled
 // vectors and the two entry points.  The tiling and the segment scheme are
 // mil_train.hip's: 64 rows per tile whatever the bag boundaries, segment (tile t, bag b) = id t + b; no float atomics.
 // The level of a row is uniform over the wave (pooling: over the workgroup) that handles it, so the per-level accumulators are
@@ -24,6 +24,7 @@
 #include "../../include/hipac_mil_levels.h"
 #include "mil_device.h"
 #include "mil_train_internal.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void ml_score_kernel(const float* __restrict__
       const int j = lane + 64 * q;
       if (j < A) v = fmaf(Uw[lev * A + j], H[(size_t)i * A_pad + j], v);
     }
-    v = mil_wave_sum(v);
+    v = wave_sum(v);
     if (lane == 0) scores[i] = v + Ub[lev];
   }
 }
@@ -73,11 +74,11 @@ __global__ __launch_bounds__(256) void ml_softmax_kernel(const float* __restrict
     if (lev == k) mx = fmaxf(mx, scores[i]);
     if (k == 0 && lev >= L) attn[i] = 0.f;
   }
-  const float m = mil_block_reduce(mx, true, red);
+  const float m = block_max_tree<4>(mx, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256)
     if (level_of[i] == k) z += expf(scores[i] - m);
-  z = mil_block_reduce(z, false, red);
+  z = block_sum_tree<4>(z, red);
   if (!(z > 0.f)) return;  // the same z in every thread
   const float inv = 1.f / z;
   for (int i = o0 + tid; i < o1; i += 256)
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void ml_ds_kernel(const float* __restrict__ fe
       const f32x4 xv = x[c], gv = gb[c];
       t = fmaf(xv[0], gv[0], t), t = fmaf(xv[1], gv[1], t), t = fmaf(xv[2], gv[2], t), t = fmaf(xv[3], gv[3], t);
     }
-    const float ds = attn[i] * (mil_wave_sum(t) - cdot[b * L + lev]);
+    const float ds = attn[i] * (wave_sum(t) - cdot[b * L + lev]);
     switch (lev) {
       case 0: ml_ds_row<L, 0>(ds, u, accU, accB, accV, hrow, lane, A, A_pad); break;
       case 1: ml_ds_row<L, 1>(ds, u, accU, accB, accV, hrow, lane, A, A_pad); break;

@@ -24,8 +24,8 @@
 #include "common.h"
 
 #include "../../include/hipac_mil_train.h"
-#include "mil_device.h"
 #include "mil_train_internal.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void mt_score_kernel(const float* __restrict__
     if (i >= n) break;
     float v = 0.f;
     for (int j = lane; j < A; j += 64) v = fmaf(Uw[j], H[(size_t)i * A_pad + j], v);
-    v = mil_wave_sum(v);
+    v = wave_sum(v);
     if (lane == 0) scores[i] = v + Ub[0];
   }
 }
@@ -171,10 +171,10 @@ __global__ __launch_bounds__(256) void mt_softmax_kernel(const float* __restrict
   const int o0 = offs[b], o1 = offs[b + 1];
   float mx = -INFINITY;
   for (int i = o0 + tid; i < o1; i += 256) mx = fmaxf(mx, scores[i]);
-  const float m = mil_block_reduce(mx, true, red);
+  const float m = block_max_tree<4>(mx, red);
   float z = 0.f;
   for (int i = o0 + tid; i < o1; i += 256) z += expf(scores[i] - m);
-  const float inv = 1.f / mil_block_reduce(z, false, red);
+  const float inv = 1.f / block_sum_tree<4>(z, red);
   for (int i = o0 + tid; i < o1; i += 256) attn[i] = expf(scores[i] - m) * inv;
 }
 
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void mt_cdot_kernel(const float* __restrict__ 
     const f32x4 pv = pb[c], gv = gb[c];
     v = fmaf(pv[0], gv[0], v), v = fmaf(pv[1], gv[1], v), v = fmaf(pv[2], gv[2], v), v = fmaf(pv[3], gv[3], v);
   }
-  v = mil_wave_sum(v);
+  v = wave_sum(v);
   if (lane == 0) cdot[b] = v;
 }
 
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256) void mt_rowdot_kernel(const float* __restrict_
       const f32x4 xv = x[c], gv = gb[c];
       t = fmaf(xv[0], gv[0], t), t = fmaf(xv[1], gv[1], t), t = fmaf(xv[2], gv[2], t), t = fmaf(xv[3], gv[3], t);
     }
-    t = mil_wave_sum(t);
+    t = wave_sum(t);
     if (lane == 0) rowdot[i] = t;
   }
 }
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void mt_bag_cdot_kernel(const float* __restric
     num += a * (double)rowdot[i];
     den += a;
   }
-  for (int o = 32; o > 0; o >>= 1) num += __shfl_down(num, o, 64), den += __shfl_down(den, o, 64);
+  num = wave_sum_tree(num), den = wave_sum_tree(den);
   if (lane == 0) red[0][wave] = num, red[1][wave] = den;
   __syncthreads();
   if (tid == 0)

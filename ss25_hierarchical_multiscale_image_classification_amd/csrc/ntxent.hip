@@ -9,6 +9,7 @@
 // back through F.normalize.  Round 2's LDS-tiled FMA kernels recomputed every tile's scores with two LDS reads per FMA on half
 // the CUs: 1.6 ms per step at 2N = 2048 against ~0.15 ms now.  No atomics: the loss is summed in row order.
 #include "common.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -21,7 +22,7 @@ __global__ __launch_bounds__(256) void ntx_normalize_kernel(const float* __restr
     const float v = z[(size_t)row * D + k];
     s = fmaf(v, v, s);
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   const float inv = 1.f / fmaxf(sqrtf(s), 1e-12f);
   for (int k = lane; k < D; k += 64) zn[(size_t)row * D + k] = z[(size_t)row * D + k] * inv;
   if (lane == 0) inv_norm[row] = inv;
@@ -36,14 +37,14 @@ __global__ __launch_bounds__(256) void ntx_lse_kernel(const float* __restrict__ 
   float m = -INFINITY;
   for (int j = tid; j < rows; j += 256)
     if (j != i) m = fmaxf(m, row[j] * inv_t);
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  m = wave_max(m);
   if ((tid & 63) == 0) red[tid >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float s = 0.f;
   for (int j = tid; j < rows; j += 256)
     if (j != i) s += expf(row[j] * inv_t - m);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   if ((tid & 63) == 0) red[4 + (tid >> 6)] = s;
   __syncthreads();
   if (tid == 0) {
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void ntx_project_kernel(const float* g, const 
   if (row >= rows) return;
   float dot = 0.f;
   for (int k = lane; k < D; k += 64) dot = fmaf(zn[(size_t)row * D + k], g[(size_t)row * D + k] * gscale, dot);
-  for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+  dot = wave_sum(dot);
   const float inv = inv_norm[row];
   for (int k = lane; k < D; k += 64)
     dz[(size_t)row * D + k] = (g[(size_t)row * D + k] * gscale - zn[(size_t)row * D + k] * dot) * inv;

@@ -29,6 +29,7 @@
 #include "common.h"
 
 #include "../../include/hipac_png.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -306,8 +307,7 @@ __global__ __launch_bounds__(kPngThreads) void png_band_kernel(const uint8_t* __
       for (int t = 0; t < 5; ++t) cost[t] += png_cost(v[t]);
     }
 #pragma unroll
-    for (int t = 0; t < 5; ++t)
-      for (int d = 32; d >= 1; d >>= 1) cost[t] += __shfl_xor(cost[t], d, 64);
+    for (int t = 0; t < 5; ++t) cost[t] = wave_sum(cost[t]);
     int best = 0;
 #pragma unroll
     for (int t = 1; t < 5; ++t)

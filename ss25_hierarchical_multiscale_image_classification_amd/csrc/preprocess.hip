@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -21,14 +22,6 @@ __device__ __forceinline__ unsigned clip8(int acc) {
   int v = acc >> kPrecisionBits;
   v = v < 0 ? 0 : v;
   return (unsigned)(v > 255 ? 255 : v);
-}
-
-__device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
 }
 
 template <typename T>
@@ -179,7 +172,7 @@ __global__ __launch_bounds__(256) void tile_resize_kernel(const uint8_t* __restr
   }
 
   if (sums != nullptr) {
-    const unsigned tot = block_sum_u32(mysum, red);
+    const unsigned tot = block_sum_tree<4>(mysum, red);
     if (tid == 0) atomicAdd(&sums[w], tot);
   }
 }
@@ -214,7 +207,7 @@ __global__ __launch_bounds__(256) void tile_identity_kernel(const uint8_t* __res
     emit_pixel(out, fmt, lut, w, oy, j, r, g, b);
   }
   if (sums != nullptr) {
-    const unsigned tot = block_sum_u32(mysum, red);
+    const unsigned tot = block_sum_tree<4>(mysum, red);
     if (tid == 0) atomicAdd(&sums[w], tot);
   }
 }

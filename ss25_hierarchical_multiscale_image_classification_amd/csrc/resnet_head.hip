@@ -1,6 +1,7 @@
 // The small kernels around the ResNet18 trunk: input conversion, the two heads (global average pool, fc, argmax) and
 // the test-only tap export, with their launchers.
 #include "resnet_handle.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -51,9 +52,7 @@ __device__ __forceinline__ void head_tail(float f0, float f1, int b, int tid, co
   if (num_classes <= 0 || (!logits && !labels)) return;
   for (int j = 0; j < num_classes; ++j) {
     const float2 w = *reinterpret_cast<const float2*>(fc_w + (size_t)j * 512 + tid * 2);
-    float v = f0 * w.x + f1 * w.y;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const float v = wave_sum_tree(f0 * w.x + f1 * w.y);
     if ((tid & 63) == 0) red[tid >> 6][j] = v;
   }
   __syncthreads();

@@ -17,6 +17,7 @@
 
 #include "../../include/hipac_stain.h"
 #include "stain_od.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -81,9 +82,7 @@ __global__ __launch_bounds__(256) void stain_moments_kernel(StainImage g, unsign
   });
 #pragma unroll
   for (int i = 0; i < 10; ++i) {
-    long long v = acc[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const long long v = wave_sum_tree(acc[i]);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][i] = v;
   }
   __syncthreads();

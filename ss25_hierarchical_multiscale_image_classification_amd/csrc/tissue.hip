@@ -17,6 +17,7 @@
 #include "common.h"
 
 #include "../../include/hipac_tissue.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -153,13 +154,7 @@ __global__ __launch_bounds__(64) void tissue_rowscan_kernel(const uint8_t* __res
   int carry = 0;
   for (int i0 = 0; i0 < mw; i0 += 64) {
     const int i = i0 + lane;
-    int v = i < mw ? mask[(size_t)j * mw + i] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(v, o, 64);
-      if (lane >= o) v += u;
-    }
-    v += carry;
+    const int v = wave_scan_incl(i < mw ? (int)mask[(size_t)j * mw + i] : 0, lane) + carry;
     if (i < mw) out[i + 1] = v;
     carry = __shfl(v, 63, 64);
   }

@@ -21,6 +21,7 @@
 // the PyTorch layout [Cout][Cin][kh][kw], then BN gamma, beta); running statistics in a second flat buffer
 // (per conv: running_mean, running_var); gradients in a buffer shaped like the parameters.
 #include "train_common.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
         nll = w * (logf(se) + mx - l[y]);
       }
     }
-    for (int o = 32; o > 0; o >>= 1) nll += __shfl_down(nll, o, 64), w += __shfl_down(w, o, 64);
+    nll = wave_sum_tree(nll), w = wave_sum_tree(w);
     // every workgroup's four wave sums, then the workgroups in order (phase 2 below): no atomics, a reproducible loss
     if ((threadIdx.x & 63) == 0) scratch[2 + 2 * (blockIdx.x * 4 + (threadIdx.x >> 6))] = nll, scratch[3 + 2 * (blockIdx.x * 4 + (threadIdx.x >> 6))] = w;
   } else if (phase == 2) {

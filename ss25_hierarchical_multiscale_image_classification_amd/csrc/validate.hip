@@ -16,6 +16,7 @@
 
 #include "../../include/hipac_validate.h"
 #include "mil_train_internal.h"
+#include "wave_reduce.h"
 
 namespace hipac {
 
@@ -52,13 +53,6 @@ static void vd_gram_slices(int n, int F, int* chunk, int* slices) {
   c = (c + kVdGramGranule - 1) / kVdGramGranule * kVdGramGranule;
   *chunk = (int)c;
   *slices = (int)((n + c - 1) / c);
-}
-
-__device__ __forceinline__ float vd_wave_sum(float v) {
-  // xor butterfly: both partners of a stage form the same sum, so every lane ends with the same bits
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 __device__ __forceinline__ float vd_dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(256) void vd_sweep_kernel(const float* __restrict__
       float dot = 0.f;
 #pragma unroll
       for (int j = 0; j < NV; ++j) dot += vd_dot4(x[q][j], wv[j]);
-      dot = vd_wave_sum(dot);
+      dot = wave_sum(dot);
       if (src[q] >= 0) {  // wave-uniform
         const float m = dot + b;
         const bool y = labels[src[q]] != 0;
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(256) void vd_project_kernel(const float* __restrict
       float dot = 0.f;
 #pragma unroll
       for (int j = 0; j < NV; ++j) dot += vd_dot4(x[0][j], wk[k][j]);
-      z[k] = vd_wave_sum(dot);
+      z[k] = wave_sum(dot);
     }
     const int y = labels ? (labels[src[0]] != 0 ? 1 : 0) : 0;
     cnt[y] += 1.f;
