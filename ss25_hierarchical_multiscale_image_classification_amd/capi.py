@@ -339,6 +339,19 @@ class PackedResNet18:
             buf = self._batch = torch.empty(need, dtype=torch.uint8, device=device)
         return buf[:need].view(n, PATCH, PATCH, 3)
 
+    def view_buffer(self, n: int, device: torch.device) -> torch.Tensor:
+        """uint8[n,224,224,3] view of a second grow-only buffer kept on the handle: where ``tta.score_views`` makes the rotated
+        and mirrored copies of ONE forward slice (1.23 GB at 8 192 patches), never of the slide.  Valid until the next call."""
+        need = n * PATCH * PATCH * 3
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device(device.type, torch.cuda.current_device())
+        buf = getattr(self, "_view", None)
+        if buf is None or buf.numel() < need or buf.device != device:
+            buf = self._view = None  # release both references before growing, as batch_buffer does
+            buf = self._view = torch.empty(need, dtype=torch.uint8, device=device)
+        return buf[:need].view(n, PATCH, PATCH, 3)
+
     def workspace(self, batch: int, device: torch.device) -> torch.Tensor:
         need = self._lib.hipac_resnet18_workspace_bytes(batch, PRECISIONS[self.precision])
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:

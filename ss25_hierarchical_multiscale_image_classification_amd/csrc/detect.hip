@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "../../include/hipac_detect.h"
+#include "detect_prob.h"
 
 namespace hipac {
 
@@ -38,8 +39,7 @@ struct GaussTaps {
 __global__ __launch_bounds__(256) void detect_probs_kernel(const float* __restrict__ logits, int n, int tumor, float* __restrict__ p) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float d = logits[2 * i + (1 - tumor)] - logits[2 * i + tumor];
-  p[i] = 1.0f / (1.0f + expf(d));
+  p[i] = tumor_prob(logits, (size_t)i, tumor);
 }
 
 __global__ __launch_bounds__(256) void detect_fill_kernel(int32_t* __restrict__ a, int n, int32_t v) {

@@ -216,7 +216,9 @@ class DetectionResult:
     """Detections of one slide.  ``prob`` float32[k], ``x`` / ``y`` int64[k] level-0 pixels (numpy, largest first); ``fused``
     the fused map before smoothing and ``smoothed`` the map NMS ran on (the same tensor when sigma = 0), both float32[gh, gw]
     on the device; ``level_maps`` / ``level_counts`` per level; ``probs`` float32[n] the tumour probability of every scored
-    window, in the order of ``meta`` int32[n, 4] = (level, x, y, label)."""
+    window, in the order of ``meta`` int32[n, 4] = (level, x, y, label).  ``views``: the number of views ``probs`` is the mean
+    of (test-time augmentation, ``tta.py``); ``tta_range`` float32[n] on the device, the largest minus the smallest per-view
+    probability of every window, None when the windows were scored in one view."""
     geometry: Geometry
     grid: Tuple[int, int]
     prob: np.ndarray
@@ -228,6 +230,8 @@ class DetectionResult:
     meta: torch.Tensor
     level_maps: Dict[int, torch.Tensor] = field(default_factory=dict)
     level_counts: Dict[int, torch.Tensor] = field(default_factory=dict)
+    views: int = 1
+    tta_range: Optional[torch.Tensor] = None
 
 
 def detections_from_scores(logits, meta, level0_size: Tuple[int, int], levels: Sequence[int] = (0, 1, 2, 3), cell: int = 224,
@@ -235,18 +239,28 @@ def detections_from_scores(logits, meta, level0_size: Tuple[int, int], levels: S
                            max_detections: int = 2000, tumor_class: int = 1, device=None) -> DetectionResult:
     """Everything after the scan: ``logits`` float32[n, 2] and ``meta`` int32[n, 4] = (level, x, y, label) as
     ``extract.score_slide`` returns them (any row order; torch or numpy, moved to the device if they are not there), of a slide
-    of ``level0_size`` = (W0, H0).  ``levels`` names the levels whose rows are used."""
+    of ``level0_size`` = (W0, H0).  ``levels`` names the levels whose rows are used.  ``logits`` float32[V, n, 2] are the
+    scores of V views of every window (``score_slide(views=...)``): ``probs`` is then their mean probability
+    (``tta.reduce``), ``tta_range`` is kept, and everything downstream is unchanged."""
     geom = geometry(cell, levels)
     check_parameters(sigma, radius, max_detections, fuse)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    lg = torch.as_tensor(logits).reshape(-1, 2).to(device=dev, dtype=torch.float32).contiguous()
+    lg = torch.as_tensor(logits)
+    n_views = lg.shape[0] if lg.dim() == 3 else 0  # 0: one view, the path through tumor_probs
+    lg = (lg.reshape(n_views, -1, 2) if n_views else lg.reshape(-1, 2)).to(device=dev, dtype=torch.float32).contiguous()
     mt = torch.as_tensor(meta).reshape(-1, 4).to(device=dev, dtype=torch.int32).contiguous()
-    if lg.shape[0] != mt.shape[0]:
-        raise capi.HipacError(f"{lg.shape[0]} logit rows but {mt.shape[0]} meta rows")
+    if lg.shape[-2] != mt.shape[0]:
+        raise capi.HipacError(f"{lg.shape[-2]} logit rows but {mt.shape[0]} meta rows")
     grid = geom.grid(level0_size)
     gw, gh = grid
     with torch.cuda.device(dev):
-        p = tumor_probs(lg, tumor_class)
+        tta_range = None
+        if n_views:
+            from . import tta
+
+            p, tta_range = tta.reduce(lg, tumor_class, want_range=True)
+        else:
+            p = tumor_probs(lg, tumor_class)
         maps = torch.empty((len(geom.levels), gh, gw), dtype=torch.float32, device=dev)
         counts = torch.empty((len(geom.levels), gh, gw), dtype=torch.int32, device=dev)
         for k, level in enumerate(geom.levels):
@@ -258,17 +272,41 @@ def detections_from_scores(logits, meta, level0_size: Tuple[int, int], levels: S
     x = ((ij[:, 0].astype(np.float64) + 0.5) * geom.cell).astype(np.int64)
     y = ((ij[:, 1].astype(np.float64) + 0.5) * geom.cell).astype(np.int64)
     return DetectionResult(geom, grid, prob, x, y, fused, smoothed, p, mt,
-                           {l: maps[k] for k, l in enumerate(geom.levels)}, {l: counts[k] for k, l in enumerate(geom.levels)})
+                           {l: maps[k] for k, l in enumerate(geom.levels)}, {l: counts[k] for k, l in enumerate(geom.levels)},
+                           max(1, n_views), tta_range)
+
+
+def range_map(result: DetectionResult, fuse: str = "mean") -> torch.Tensor:
+    """float32[gh, gw] map of where the views of a test-time augmented scan disagree: ``result.tta_range`` taken through the
+    ``level_map`` and ``fuse_maps`` calls the probabilities go through (per cell the mean over the covering windows of a level,
+    then ``fuse`` over the levels with data).  HipacError for a result of one view."""
+    if result.tta_range is None:
+        raise capi.HipacError("range_map: the result has one view (detect_slide(tta=...) with rot4 or d4 keeps the range)")
+    geom, (gw, gh) = result.geometry, result.grid
+    dev = result.tta_range.device
+    with torch.cuda.device(dev):
+        maps = torch.empty((len(geom.levels), gh, gw), dtype=torch.float32, device=dev)
+        counts = torch.empty((len(geom.levels), gh, gw), dtype=torch.int32, device=dev)
+        for k, level in enumerate(geom.levels):
+            maps[k], counts[k] = level_map(result.tta_range, result.meta, level, geom, result.grid)
+        return fuse_maps(maps, counts, fuse)
 
 
 @torch.no_grad()
 def detect_slide(slide, net, levels: Sequence[int] = (0, 1, 2, 3), cell: int = 224, fuse: str = "mean", sigma: float = 1.0,
                  radius: int = 4, threshold: float = 0.5, max_detections: int = 2000, tumor_class: int = 1,
-                 tissue=None) -> DetectionResult:
+                 tissue=None, tta: str = "none") -> DetectionResult:
     """Dense scan of ``slide`` (``extract.DeviceSlide``) with the two-class ``net`` at every level of ``levels`` and the
     detection stage over the logits.  ``tissue`` (``tissue.TissueFilter``, default None = the whiteness test): the windows
-    are chosen by the slide's Otsu tissue mask, one mask for all levels."""
+    are chosen by the slide's Otsu tissue mask, one mask for all levels.  ``tta`` (``tta.MODES``: none, rot4, d4): score every
+    window in 1, 4 or 8 views of the square and average the tumour probabilities; about as many scans as views."""
+    from . import tta as tta_mod
     from .extract import score_slide
+
+    if tta not in tta_mod.MODES:
+        raise ValueError(f"tta must be one of {sorted(tta_mod.MODES)}, got {tta!r}")
+    views = tta_mod.MODES[tta]
+    scan_args = {"views": views} if len(views) > 1 else {}  # tta="none": the call of before, argument for argument
 
     geom = geometry(cell, levels)
     check_parameters(sigma, radius, max_detections, fuse)
@@ -282,10 +320,13 @@ def detect_slide(slide, net, levels: Sequence[int] = (0, 1, 2, 3), cell: int = 2
     # level is scored, so four dense levels of a large slide held at once could reach tens of GB (an estimate from the window
     # counts, not a measurement)
     for level in geom.levels:
-        _, lg, _, mt = score_slide(slide, net, levels=(level,), stride=geom.stride(level), tissue=tissue)
+        _, lg, _, mt = score_slide(slide, net, levels=(level,), stride=geom.stride(level), tissue=tissue, **scan_args)
         if lg is not None and mt.shape[0]:
             logits.append(lg), metas.append(mt)
-    lg = torch.cat(logits) if logits else torch.empty((0, 2), dtype=torch.float32, device=dev)
+    if len(views) > 1:
+        lg = torch.cat(logits, dim=1) if logits else torch.empty((len(views), 0, 2), dtype=torch.float32, device=dev)
+    else:
+        lg = torch.cat(logits) if logits else torch.empty((0, 2), dtype=torch.float32, device=dev)
     mt = torch.cat(metas) if metas else torch.empty((0, 4), dtype=torch.int32, device=dev)
     return detections_from_scores(lg, mt, slide.level_dimensions[0], geom.levels, cell, fuse, sigma, radius, threshold, max_detections,
                                   tumor_class, device=dev)

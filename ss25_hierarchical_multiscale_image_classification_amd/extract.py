@@ -382,13 +382,17 @@ class WSIPatchStream:
 
 @torch.no_grad()
 def score_slide(slide: DeviceSlide, net: capi.PackedResNet18, levels: Sequence[int] = (0, 1, 2, 3),
-                batch_windows: int = 4096, stride=None, want_logits: bool = True, fwd_batch: int = 8192, tissue=None):
+                batch_windows: int = 4096, stride=None, want_logits: bool = True, fwd_batch: int = 8192, tissue=None,
+                views: Sequence[int] = (0,)):
     """Whole-slide hierarchical scan: windows -> whiteness/labels -> resize -> ResNet18 ->
     per-patch features / logits / labels.  ``stride``: None (reference: 224), an int, or a callable level -> stride.
     Returns device tensors (feats[n,512], logits[n,C] or None, pred int64[n] or None,
     meta int32[n,4] = (level, x, y, label)) in level-major, reference visiting order.
     ``tissue`` (``tissue.TissueFilter``, default None = the whiteness test) selects the windows with the slide's Otsu tissue
     mask instead; its stages are queued on the same stream ahead of the decisions and add no wait of the host.
+    ``views`` (test-time augmentation, ``tta.MODES``): with more than the default view 0 every window is also scored rotated
+    and mirrored (``tta.score_views``, two-class networks), the logits are float32[V, n, 2], and ``feats`` and ``pred`` are
+    those of view 0.  The default takes the path below unchanged.
 
     Three phases on the caller's stream, ONE wait of the host per slide:
       1. the extractor's decisions for every requested level (whole-level kernels: resample planes, whiteness sums,
@@ -444,6 +448,15 @@ def score_slide(slide: DeviceSlide, net: capi.PackedResNet18, levels: Sequence[i
                 done += idx.shape[0]
     del lws  # the resampled planes (GBs at level 0) go back to the allocator before the forwards allocate
     t_dbg = _mark("gather", t_dbg)
+    if tuple(views) != (0,):
+        from . import tta
+
+        if not has_fc:
+            raise capi.HipacError("score_slide: views need a network with a classifier head and want_logits")
+        with trace.span(f"resnet18 forward, {len(views)} views"):
+            feats, logits, preds = tta.score_views(net, buf, views, fwd_batch=FWD, want_labels=True)
+        _mark("forwards", t_dbg)
+        return feats, logits, preds, metas
     out_chunks = []
     for lo in range(0, n_total, FWD):
         end = min(n_total, lo + FWD)

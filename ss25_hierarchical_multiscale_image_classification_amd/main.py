@@ -24,7 +24,11 @@ suppression run on the device; one ``probability,x,y`` line per detection goes t
 ``./models/first_model/model_predictions_csv/<case>.csv`` (``--detect_save_maps``: the fused map to
 ``./models/first_model/heatmaps/<case>.npy``).  ``--detect_cell`` / ``--detect_fuse`` / ``--detect_sigma`` /
 ``--detect_radius`` / ``--detect_threshold`` / ``--detect_max`` set the post-processing; under ``--world_size N`` the slides
-are sharded.  ``--detect --run_evaluation`` detects first, then scores.
+are sharded.  ``--detect --run_evaluation`` detects first, then scores.  ``--detect_tta {none,rot4,d4}`` (``tta.py``) scores every
+window in 1, 4 or 8 views of the square -- the rotations by 90 degrees, with ``d4`` each also mirrored -- made on the device from
+the patch buffer, and averages the tumour probabilities: about as many scans as views.  The slide's line then ends with
+``, V views`` and ``--detect_save_maps`` also writes ``heatmaps/<case>_tta_range.npy``, the map of the per-window range over the
+views.  Default ``none``: no byte written or printed changes.
 
 ``--tissue_filter otsu`` replaces the whiteness test (``mean > 240``, the reference's rule and the default ``white``) with an
 Otsu tissue mask made on the device (``tissue.py``): a saturation threshold on a 1 : 32 thumbnail of the coarsest level, a 3 x 3
@@ -165,6 +169,20 @@ def check_png_args(parser, args):
         parser.error(f"--png_encoder {args.png_encoder} is an option of --patch --write_png")
 
 
+def check_tta_args(parser, args):
+    """--detect_tta without --detect is refused as an argparse error (exit status 2): the views are an option of the detector
+    alone, and a flag that is dropped silently would be worse than none."""
+    if args.detect_tta != "none" and not args.detect:
+        parser.error(f"--detect_tta {args.detect_tta} is an option of --detect")
+
+
+def tta_views(args):
+    """The views of --detect_tta as ``detect_slide`` and ``score_slide`` number them (``tta.MODES``)."""
+    from . import tta
+
+    return tta.MODES[args.detect_tta]
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="HiPAC hot path on MI355X (patch extraction + ResNet18 scoring)")
     # --- the reference's surface (src/main.py:1075-1093) ---
@@ -289,6 +307,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--detect_threshold", type=float, default=0.5, help="smallest probability of a detection")
     p.add_argument("--detect_max", type=int, default=2000, help="most detections per slide")
     p.add_argument("--detect_save_maps", action="store_true", help="also write models/first_model/heatmaps/<case>.npy (float32[gh][gw])")
+    p.add_argument("--detect_tta", choices=["none", "rot4", "d4"], default="none",
+                   help="--detect: average the tumour probability of every window over its 4 rotations (rot4) or its 8 rotations "
+                        "and mirror images (d4), made on the device; about as many scans as views")
     p.add_argument("--tissue_filter", choices=["white", "otsu"], default="white",
                    help="which windows are kept: white = the reference's mean > 240 test, otsu = an Otsu saturation mask of the slide")
     p.add_argument("--tissue_min", type=float, default=0.05, help="otsu: smallest tissue fraction of a window's mask rectangle (0..1)")
@@ -611,6 +632,7 @@ def cmd_detect(args):
     if args.detect_save_maps:
         os.makedirs(map_dir, exist_ok=True)
     rank, world = rank_world()  # N > 1: every rank detects on the slides it owns and writes their files
+    tta_args = {"tta": args.detect_tta} if args.detect_tta != "none" else {}  # none: the call of before, argument for argument
     for i in shard_units(len(slides), rank, world):
         name = slides[i][0]
         slide = try_open(name, slides[i][1])
@@ -619,12 +641,14 @@ def cmd_detect(args):
         normalize_stain(args, stain, tissue, slide)
         res = detect.detect_slide(slide, net, levels=geom.levels, cell=geom.cell, fuse=args.detect_fuse, sigma=args.detect_sigma,
                                   radius=args.detect_radius, threshold=args.detect_threshold, max_detections=args.detect_max,
-                                  tissue=tissue)
+                                  tissue=tissue, **tta_args)
         n = detect.save_detection_csv(os.path.join(csv_dir, name + ".csv"), res)
         if args.detect_save_maps:
             np.save(os.path.join(map_dir, name + ".npy"), res.fused.cpu().numpy())
+            if tta_args:
+                np.save(os.path.join(map_dir, name + "_tta_range.npy"), detect.range_map(res, args.detect_fuse).cpu().numpy())
         print(f"[INFO] {name}: {res.probs.shape[0]} windows at levels {list(geom.levels)}, map {res.grid[0]} x {res.grid[1]} cells of "
-              f"{geom.cell} px, {n} detections", flush=True)
+              f"{geom.cell} px, {n} detections" + (f", {res.views} views" if tta_args else ""), flush=True)
         report_tissue(args, tissue, slide)
         report_stain(args, stain, tissue, slide)
     return 0
@@ -908,6 +932,7 @@ def main(argv=None) -> int:
     check_aug_args(parser, args)
     check_eval_patches_args(parser, args)
     check_png_args(parser, args)
+    check_tta_args(parser, args)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")
