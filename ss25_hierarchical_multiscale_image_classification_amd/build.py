@@ -25,7 +25,7 @@ LIB = PKG / os.environ.get("HIPAC_LIB_NAME", "libhipac_hip.so")
 SOURCES = ["hipac_capi.hip", "resnet_pack.hip", "resnet_forward.hip", "resnet_head.hip", "preprocess.hip", "level_planes.hip", "mil.hip", "ntxent.hip", "conv_bf16.hip", "conv_f16.hip",
            "conv_f32.hip", "conv_f16x3.hip", "conv_f16q8.hip", "train.hip", "train_amp.hip", "augment.hip", "jpeg_decode.hip", "froc.hip",
            "mil_train.hip", "mil_dropout.hip", "mil_heads.hip", "mil_gated.hip", "mil_levels.hip", "detect.hip", "tissue.hip", "stain.hip", "lzw.hip", "deflate.hip",
-           "validate.hip", "eval_ci.hip", "evaluate.hip", "png_encode.hip", "tta.hip"]
+           "validate.hip", "eval_ci.hip", "evaluate.hip", "png_encode.hip", "tta.hip", "knn.hip"]
 PUBLIC_HEADERS = [PKG.parent / "include" / "hipac.h", PKG.parent / "include" / "hipac_eval.h",
                   PKG.parent / "include" / "hipac_mil_train.h", PKG.parent / "include" / "hipac_detect.h",
                   PKG.parent / "include" / "hipac_tissue.h", PKG.parent / "include" / "hipac_stain.h",
@@ -35,7 +35,7 @@ PUBLIC_HEADERS = [PKG.parent / "include" / "hipac.h", PKG.parent / "include" / "
                   PKG.parent / "include" / "hipac_validate.h", PKG.parent / "include" / "hipac_eval_ci.h",
                   PKG.parent / "include" / "hipac_pair_tap.h", PKG.parent / "include" / "hipac_augment_hed.h",
                   PKG.parent / "include" / "hipac_evaluate.h", PKG.parent / "include" / "hipac_png.h",
-                  PKG.parent / "include" / "hipac_tta.h"]
+                  PKG.parent / "include" / "hipac_tta.h", PKG.parent / "include" / "hipac_knn.h"]
 ARCH = "gfx950"
 # -ffp-contract=off: the host-side Pillow coefficient restatement must round every
 # double operation separately (no fused multiply-add), see preprocess.hip.

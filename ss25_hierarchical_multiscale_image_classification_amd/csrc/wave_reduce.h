@@ -4,6 +4,7 @@
 // Wave level: the 64 lanes of a wave, no LDS, no barrier; every lane of the wave must make the call.
 //   wave_sum / wave_max / wave_min   xor butterfly, distances 32, 16, ..., 1.  Both partners of a stage form the same value, so
 //                                    every lane ends with the result, bit for bit the same.
+//   wave_umax                        the same butterfly with max over an unsigned integer type (32 or 64 bits).
 //   wave_sum_tree / wave_max_tree    __shfl_down tree, distances 32, 16, ..., 1.  The result is defined in lane 0 only.  Stage
 //                                    by stage lane 0 combines the same two partial results as in the butterfly, so it holds the
 //                                    same bits; the other lanes do not.  A site keeps the form it was written with.
@@ -15,6 +16,7 @@
 // every thread gets the result.  Lane 0 of wave w writes its wave's result r_w to scratch[w]; after a barrier every thread
 // combines them in wave order, ((r_0 op r_1) op r_2) op r_3; a second barrier ends the call.
 //   block_sum / block_min            integers; butterfly inside the wave.
+//   block_umax                       unsigned integers, 32 or 64 bits; butterfly inside the wave.
 //   block_sum_tree / block_max_tree  tree inside the wave; the fixed-order reduction of the float kernels (sum or max).
 //   block_scan_excl                  exclusive prefix sum of one integer per thread in thread order, and the workgroup's total
 //                                    (the waves' totals go through the scratch: lane 63 writes).
@@ -50,6 +52,16 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+template <class T>
+__device__ __forceinline__ T wave_umax(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T u = __shfl_xor(v, o, 64);
+    v = u > v ? u : v;
+  }
   return v;
 }
 
@@ -97,6 +109,11 @@ __device__ __forceinline__ T block_sum(T v, void* scratch) {
 template <int WAVES>
 __device__ __forceinline__ int block_min(int v, void* scratch) {
   return block_combine<WAVES>(wave_min(v), scratch, [](int a, int b) { return min(a, b); });
+}
+
+template <int WAVES, class T>
+__device__ __forceinline__ T block_umax(T v, void* scratch) {
+  return block_combine<WAVES>(wave_umax(v), scratch, [](T a, T b) { return a > b ? a : b; });
 }
 
 template <int WAVES, class T>

@@ -84,6 +84,7 @@ then not read.  ``--predict_mil`` reads the levels from the saved model; ``--mil
 ``--validate`` is the reference's feature sanity check (src/main.py:1017-1070) on the device: a two-component PCA and a
 class-weighted logistic-regression probe (Newton's method) on ``patch_features_<L>.npy`` / ``patch_labels_<L>.npy`` of
 ``--patch_level`` -> ``results/validate_<L>.json``; ``--validate_save_pca`` adds ``results/pca_<L>.npy``.  No t-SNE.
+``--validate_knn K`` adds the weighted k-nearest-neighbour probe (knn.py); ``--validate_save_knn`` its neighbour table.
 
 ``--eval_patches`` is the reference's ``--evaluate`` stage (src/main.py:974-1015) under a new name (``--evaluate`` itself
 stays out of scope): the checkpoint of ``--weights`` (default ``src/models/resnet18_patch_classifier.pth``, where ``--train``
@@ -174,6 +175,31 @@ def check_tta_args(parser, args):
     alone, and a flag that is dropped silently would be worse than none."""
     if args.detect_tta != "none" and not args.detect:
         parser.error(f"--detect_tta {args.detect_tta} is an option of --detect")
+
+
+def _validate_knn(text: str) -> int:
+    v = int(text)
+    if not 1 <= v <= 256:
+        raise argparse.ArgumentTypeError(f"takes a neighbour count in 1..256, got {text}")
+    return v
+
+
+def _validate_knn_T(text: str) -> float:
+    v = float(text)
+    if not 0.01 <= v <= 10.0:
+        raise argparse.ArgumentTypeError(f"takes a temperature in 0.01..10, got {text}")
+    return v
+
+
+def check_validate_knn_args(parser, args):
+    """--validate_knn / --validate_knn_T / --validate_save_knn without --validate, and the latter two without --validate_knn,
+    are refused as argparse errors (exit status 2): a flag that is dropped silently would be worse than none."""
+    given = [name for name, on in (("--validate_knn", args.validate_knn is not None), ("--validate_knn_T", args.validate_knn_T is not None),
+                                   ("--validate_save_knn", args.validate_save_knn)) if on]
+    if given and not args.validate:
+        parser.error(f"{given[0]} is an option of --validate")
+    if args.validate_knn is None and given:
+        parser.error(f"{given[0]} needs --validate_knn K")
 
 
 def tta_views(args):
@@ -325,6 +351,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--validate_save_pca", action="store_true",
                    help="--validate: also write results/pca_<L>.npy, float32 [N, 2], row i = the two PCA coordinates of line i of "
                         "patch_paths_<L>.txt")
+    p.add_argument("--validate_knn", type=_validate_knn, default=None, metavar="K",
+                   help="--validate: also the weighted k-nearest-neighbour probe (Wu et al. 2018) with K neighbours (1..256) on the "
+                        "probe's split, searched on the device; absent = off")
+    p.add_argument("--validate_knn_T", type=_validate_knn_T, default=None, metavar="T",
+                   help="--validate_knn: the temperature of the neighbour weights exp((s - s_best) / T), 0.01..10 (default 0.07)")
+    p.add_argument("--validate_save_knn", action="store_true",
+                   help="--validate_knn: also write results/knn_<L>.npy, int32 [n_test, 1 + K]: a test row and its K neighbours, "
+                        "nearest first, as line numbers of patch_paths_<L>.txt")
     p.add_argument("--validate_C", type=float, default=1.0, help="--validate: inverse regularisation strength of the probe (> 0)")
     p.add_argument("--validate_tol", type=float, default=1e-4, help="--validate: the probe stops at max |gradient| <= this")
     p.add_argument("--_child", action="store_true", help=argparse.SUPPRESS)
@@ -841,13 +875,16 @@ def cmd_validate(args) -> int:
             continue
         print(f"[INFO] Label distribution (0=normal, 1=tumor): {np.bincount(labels)}")
         res = validate.run(features, labels, seed=42 if args.seed is None else args.seed, C_reg=args.validate_C,
-                           tol=args.validate_tol)
+                           tol=args.validate_tol, knn_k=args.validate_knn or 0,
+                           knn_temperature=0.07 if args.validate_knn_T is None else args.validate_knn_T)
         doc = validate.report(res)
         os.makedirs("results", exist_ok=True)
         with open(os.path.join("results", f"validate_{level}.json"), "w") as f:
             json.dump(doc, f, indent=2)
         if args.validate_save_pca:
             np.save(os.path.join("results", f"pca_{level}.npy"), res["projection"])
+        if args.validate_save_knn and "knn" in res:
+            np.save(os.path.join("results", f"knn_{level}.npy"), res["knn"]["neighbours"])
     return rc
 
 
@@ -933,6 +970,7 @@ def main(argv=None) -> int:
     check_eval_patches_args(parser, args)
     check_png_args(parser, args)
     check_tta_args(parser, args)
+    check_validate_knn_args(parser, args)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             print(f"[ERROR] --{name} is outside the accelerated hot path (see DESIGN.md 'Out of scope').")

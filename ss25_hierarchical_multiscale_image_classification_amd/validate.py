@@ -13,6 +13,9 @@ Here the feature matrix goes to the device once and stays there:
   (F + 1) x (F + 1) solve runs on the host in float64.  The training and the test rows are index lists into the one
   matrix.
 
+* the k-NN probe (``knn_k`` > 0, knn.py): the weighted k-nearest-neighbour classifier of Wu et al. 2018 on the probe's split
+  and under its class weights; the search runs on the device and keeps K numbers per test row.
+
 Deliberately different from the reference: no t-SNE; our own split (``stratified_split``), not scikit-learn's shuffle;
 Newton instead of L-BFGS (the objective is strictly convex: same optimum); eigen-decomposition of the covariance
 instead of an SVD of the centred matrix; float32 sums on the device.
@@ -308,13 +311,28 @@ def fit_probe(X: torch.Tensor, labels: torch.Tensor, train_rows: torch.Tensor, c
             "gradient_norm": float(np.max(np.abs(g))), "converged": converged, "loss": float(J)}
 
 
-def run(features, labels, seed: int = 42, C_reg: float = 1.0, tol: float = 1e-4, max_iter: int = 100, device=None
-        ) -> Dict[str, object]:
+def knn_probe(X: torch.Tensor, y: torch.Tensor, lab: np.ndarray, train: np.ndarray, test: np.ndarray, train_rows: torch.Tensor,
+              test_rows: torch.Tensor, class_w: np.ndarray, k: int, temperature: float) -> Dict[str, object]:
+    """The weighted k-NN classifier (knn.py) on the probe's split, under the probe's class weights.  -> k, temperature,
+    n_train, n_test, the metrics of ``classification_metrics`` on the test rows and ``neighbours`` int32 [n_test, 1 + k]: a
+    test row number, then the row numbers of its neighbours, nearest first."""
+    from . import knn
+
+    r = knn.knn_classify(X, y, train_rows, test_rows, k, temperature, class_w)
+    out: Dict[str, object] = {"k": int(k), "temperature": float(temperature), "n_train": int(train.size), "n_test": int(test.size)}
+    out.update(classification_metrics(lab[test], r["pred"].cpu().numpy().astype(np.int64)))
+    out["neighbours"] = np.concatenate([test.astype(np.int32)[:, None], r["neighbours"].cpu().numpy()], axis=1)
+    return out
+
+
+def run(features, labels, seed: int = 42, C_reg: float = 1.0, tol: float = 1e-4, max_iter: int = 100, device=None, knn_k: int = 0,
+        knn_temperature: float = 0.07) -> Dict[str, object]:
     """The whole check on ``features`` float32 [N, F] and ``labels`` (0 / 1) [N].  -> a dict with the PCA
     (explained_variance_ratio, pca_class_means, components, projection as a float32 numpy array) and, when both classes
     have at least two rows, the probe (n_train, n_test, the metrics of ``classification_metrics`` on the test rows,
     newton_iterations, gradient_norm, converged, coef, intercept, test_rows, test_margins); otherwise ``probe_skipped``
-    holds the reason."""
+    holds the reason.  With ``knn_k`` > 0 and the probe's split, ``knn`` holds the result of ``knn_probe``, or
+    ``knn_skipped`` the reason why not."""
     lab = check_labels(labels)
     feats = np.ascontiguousarray(features, dtype=np.float32)
     if feats.ndim != 2 or feats.shape[0] != lab.shape[0] or feats.shape[0] == 0:
@@ -333,6 +351,8 @@ def run(features, labels, seed: int = 42, C_reg: float = 1.0, tol: float = 1e-4,
         train, test = stratified_split(lab, seed)
     except ValueError as e:
         out["probe_skipped"] = str(e)
+        if knn_k > 0:
+            out["knn_skipped"] = str(e)
         return out
     train_rows = torch.from_numpy(train.astype(np.int32)).to(dev)
     test_rows = torch.from_numpy(test.astype(np.int32)).to(dev)
@@ -347,6 +367,11 @@ def run(features, labels, seed: int = 42, C_reg: float = 1.0, tol: float = 1e-4,
     out.update({"n_train": int(train.size), "n_test": int(test.size), "newton_iterations": fit["iterations"],
                 "gradient_norm": fit["gradient_norm"], "converged": bool(fit["converged"]), "coef": fit["coef"],
                 "intercept": fit["intercept"], "test_rows": test, "test_margins": margins})
+    if knn_k > 0:
+        if train.size < knn_k:
+            out["knn_skipped"] = f"{train.size} training row(s): k = {knn_k} needs at least as many"
+        else:
+            out["knn"] = knn_probe(X, y, lab, train, test, train_rows, test_rows, class_w, knn_k, knn_temperature)
     return out
 
 
@@ -367,9 +392,21 @@ def report(res: Dict[str, object]) -> Dict[str, object]:
         print(f"[INFO] Logistic Regression Accuracy: {res['accuracy']:.4f}")
         print("[INFO] Confusion Matrix:")
         print(np.array([[cm["TN"], cm["FP"]], [cm["FN"], cm["TP"]]]))
+    if "knn" in res:
+        kn = res["knn"]
+        cm = kn["confusion_matrix"]
+        print(f"[INFO] k-NN (k = {kn['k']}, T = {kn['temperature']:g}) accuracy: {kn['accuracy']:.4f}")
+        print("[INFO] k-NN Confusion Matrix:")
+        print(np.array([[cm["TN"], cm["FP"]], [cm["FN"], cm["TP"]]]))
+    elif "knn_skipped" in res:
+        print(f"[INFO] k-NN probe skipped: {res['knn_skipped']}.")
     doc = {k: res[k] for k in JSON_KEYS if k in res}
     # an absent class has no mean: null in the file, not NaN
     doc["pca_class_means"] = [[None if v != v else v for v in row] for row in doc["pca_class_means"]]
     if "probe_skipped" in res:
         doc["probe_skipped"] = res["probe_skipped"]
+    if "knn" in res:
+        doc["knn"] = {k: v for k, v in res["knn"].items() if k != "neighbours"}
+    elif "knn_skipped" in res:
+        doc["knn_skipped"] = res["knn_skipped"]
     return doc
